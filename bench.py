@@ -7,6 +7,8 @@ previous block (projectAndNormalize), and the host T extension; diagnostics
 resident in HBM before the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload lap3d_215]
+  python bench.py --full                                    # + legs, roofline, CPU baselines
+  python bench.py --dump-outputs DIR                        # + DIR/<name>.npy of the last timed step
   python bench.py --workload circuit_1259 --driver irl      # BASELINE config 5
   python bench.py --matrix G3_circuit.mtx --driver irl      # a SuiteSparse file
 
@@ -18,6 +20,14 @@ per outer iteration (CA matrix powers, overlapped with the interior powers)
 and RCCL allreduce of the Gram blocks (strong scaling, whole-job rate).
 --driver irl times whole impl_restarted_ca_lanczos solves instead of
 ca_lanczos outer iterations (a secondary line; the default is the headline).
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(metric, value, unit, ms_per_step, the configuration).  --full adds everything
+else the benchmark measures, each in runs of its own after the timed steps:
+the per-kernel HIP-event timers and the roofline, the secondary legs (TSQR
+normalize, CSR format, 'full' orthogonalisation, the other workloads, the
+IRL), the back-to-back SpMV kernels, the diagnostics-on rate and the CPU
+baselines (--no-legs / --no-cpu-baseline trim a --full run).
 """
 from __future__ import annotations
 
@@ -42,8 +52,16 @@ def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
                    help="ranks (one per GPU); without a launcher bench.py starts torch.distributed.run itself")
-    p.add_argument("--steps", type=int, default=15)
-    p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--steps", type=int, default=None,
+                   help="timed steps (default 15 outer iterations; --driver irl: 5 solves)")
+    p.add_argument("--warmup", type=int, default=None,
+                   help="untimed steps before them (default 2; --driver irl: 1 solve)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the per-kernel timers / roofline, the secondary legs, "
+                        "the diagnostics-on run and the CPU baselines (a plain run prints the headline only)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed as DIR/<name>.npy (float64; large arrays as a "
+                        "fixed seeded row sample, at most 64 MB in all)")
     p.add_argument("--workload", default="lap3d_215", help="lap2d_N | lap3d_N | circuit_N")
     p.add_argument("--matrix", default=None, help="matrix file (.mtx[.gz] or SuiteSparse .mat); overrides --workload")
     p.add_argument("--driver", default="lanczos", choices=["lanczos", "irl"])
@@ -52,7 +70,7 @@ def parse():
     p.add_argument("--s", type=int, default=8)
     p.add_argument("--basis", default="newton")
     p.add_argument("--orth", default="local")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     p.add_argument("--basis-gb", type=float, default=200.0,
                    help="per-GPU budget for the Krylov basis Q; longer runs continue in restarted epochs")
     p.add_argument("--cpu-iters", type=int, default=15, help="outer iterations of the C/OpenMP CPU sample")
@@ -62,11 +80,19 @@ def parse():
     p.add_argument("--normalize", default="auto", choices=["auto", "tsqr", "cholqr2"],
                    help="normalize (tsqr.m) backend of the headline: auto = CholQR2 fused into the sweeps "
                         "(Householder TSQR when its Cholesky fails), tsqr = Householder TSQR tree")
-    p.add_argument("--no-legs", action="store_true", help="skip the secondary TSQR / CSR legs")
+    p.add_argument("--no-legs", action="store_true", help="--full without the secondary TSQR / CSR legs")
     p.add_argument("--comm", default="rccl", choices=["rccl", "host"],
                    help="N > 1 transport: RCCL (default) or host-staged gloo callbacks (rehearsal of the "
                         "distributed bench with several ranks on one GPU)")
-    return p.parse_args()
+    args = p.parse_args()
+    irl = args.driver == "irl"
+    if args.steps is None:
+        args.steps = 5 if irl else 15
+    if args.warmup is None:
+        args.warmup = 1 if irl else 2
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Workload:
@@ -598,6 +624,47 @@ def launch_ranks(args):
     return proc.returncode
 
 
+DUMP_Q_BYTES = 48 * 1000 * 1000  # of --dump-outputs' 64 MB: the row sample of the last block of Q
+DUMP_T_ORDER = 1024  # T's trailing corner (8 MB at most)
+DUMP_SEED = 5489
+
+
+def _save(dirpath, name, a):
+    np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def dump_lanczos(ctx, dirpath):
+    """--dump-outputs of the CA-Lanczos driver: what a caller of the timed
+    path receives after its last step.  T (its trailing DUMP_T_ORDER corner
+    when larger), the reorthogonalisation flags, and the s basis vectors the
+    last step appended to Q (this rank's rows; beyond DUMP_Q_BYTES a sorted
+    row sample drawn with a fixed seed, the rows stored beside it)."""
+    os.makedirs(dirpath, exist_ok=True)
+    k, s, _ = ctx.lanczos_state()
+    T, _, _, flags, _ = ctx.lanczos_get()
+    m = min(T.shape[0], DUMP_T_ORDER)
+    _save(dirpath, "T", T[T.shape[0] - m:, T.shape[1] - m:])
+    _save(dirpath, "reorth_flags", flags)
+    n = ctx.n
+    cap = DUMP_Q_BYTES // (8 * s)
+    rows = np.arange(n) if n <= cap else np.sort(np.random.RandomState(DUMP_SEED).choice(n, cap, replace=False))
+    Q = np.empty((len(rows), s))
+    for j in range(s):  # a column at a time: the whole block is 0.6 GB at n = 10M
+        Q[:, j] = ctx.lanczos_get_Q(s * (k - 1) + 1 + j, 1)[rows, 0]
+    _save(dirpath, "Q_last_block", Q)
+    _save(dirpath, "Q_last_block_rows", rows)
+
+
+def dump_irl(out, dirpath):
+    """--dump-outputs of the IRL driver: the last timed solve's eigenvalues
+    and per-restart Ritz estimates (Q_conv stays on the device in the timed
+    solves) and its restart count."""
+    os.makedirs(dirpath, exist_ok=True)
+    _save(dirpath, "conv_eigs", out["conv_eigs"])
+    _save(dirpath, "ritz_est", out["ritz_est"])
+    _save(dirpath, "num_restarts", np.array([out["num_restarts"]]))
+
+
 def main():
     args = parse()
     world_env = os.environ.get("WORLD_SIZE")
@@ -673,6 +740,10 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:
+        dump_lanczos(ctx, args.dump_outputs)
+    if not args.full:
+        return finish_plain(args, E, wd, elapsed, list(ep["flags"]) + list(ctx.lanczos_get()[3]))
     ctx.timer_enable(True)
     ctx.timer_reset()
     ctx.comm_stats(reset=True)
@@ -943,6 +1014,47 @@ def main():
         wd.done()
 
 
+def finish_plain(args, E, wd, elapsed, flags):
+    """The line of a plain run (no --full): the headline of the K timed steps
+    (max over ranks) and what describes them without a further run."""
+    world, rank, wl, dist, ctx = (E[k] for k in ("world", "rank", "wl", "dist", "ctx"))
+    K, W, s = args.steps, args.warmup, args.s
+    elapsed = max_over_ranks(dist, [elapsed])[0]
+    if wd is not None:
+        wd.enter("finalize", stage_limit("finalize"))
+    if rank == 0:
+        fmt, npat, nent = ctx.spmv_format()
+        npairpat, npent, nsplit = ctx.spmv_pair_info()
+        mpk = ctx.mpk_info()
+        emit({
+            "metric": "CA-Lanczos outer-iters/sec (n~10M, s=8)",
+            "value": K / elapsed,
+            "unit": "outer-iters/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": 1e3 * elapsed / K,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": wl.data,
+            "config": {"workload": wl.desc % (wl.n, E["nnz_total"]),
+                       "s": s, "basis": args.basis, "orth": args.orth, "parallelism": "row-slab x%d" % world,
+                       "normalize": args.normalize, "comm": (args.comm if world > 1 else "none"),
+                       "halo": ("%s (CA matrix powers depth %d, band %d rows)"
+                                % (ctx.MPK_SCHEDULES.get(ctx.mpk_schedule(), "?"), mpk["depth"], mpk["band_l"]))
+                               if world > 1 else "none"},
+            "spmv_format": ("%s (%d row patterns, %d entries; %d pair patterns, %d entries, %d split pairs)"
+                            % (fmt, npat, nent, npairpat, npent, nsplit)) if fmt == "pattern" else fmt,
+            "reorth_passes": "%d/%d" % (int(np.sum(flags[W:W + K])), K),
+        })
+    if dist is not None:
+        dist.barrier()
+    if wd is not None:
+        wd.done()
+
+
 def timed_leg(ctx, r, s, K, W, basis, orth, dist):
     """A secondary leg on the same workload: a fresh run, W warm-up and K
     timed outer iterations (barrier + synchronize on both sides, max over
@@ -1132,10 +1244,10 @@ def diagnostics_run(ctx, r, s, args, t=15):
                     "the orthogonality error after every outer iteration, as the reference always runs"}
 
 
-def irl_measure(cal, ctx, r_loc, ml, nw, s, basis, tol, K, W, dist):
+def irl_measure(cal, ctx, r_loc, ml, nw, s, basis, tol, K, W, dist, full=True):
     """Time K whole impl_restarted_ca_lanczos solves after W warm-up solves
-    (barrier + synchronize on both sides, max over ranks), then one solve
-    with the per-kernel HIP-event timers and one that downloads Q_conv."""
+    (barrier + synchronize on both sides, max over ranks), then (full) one
+    solve with the per-kernel HIP-event timers and one that downloads Q_conv."""
     # k kept, p shifts, m = k + p (impl_restarted_ca_lanczos.m:72-74, k >= s; include/calanczos.h)
     k = max(nw + 4, s)
     p = s * ((ml - k) // s)
@@ -1162,6 +1274,10 @@ def irl_measure(cal, ctx, r_loc, ml, nw, s, basis, tol, K, W, dist):
     elapsed = time.perf_counter() - t0
     if dist is not None:
         dist.barrier()
+    if not full:
+        return {"k": k, "p": p, "m": m, "out": out, "elapsed": max_over_ranks(dist, [elapsed])[0],
+                "blocks": blocks, "K": K}
+    last = out
     ctx.timer_enable(True)
     ctx.timer_reset()
     out = solve()
@@ -1178,7 +1294,7 @@ def irl_measure(cal, ctx, r_loc, ml, nw, s, basis, tol, K, W, dist):
     elapsed, spmv_avg_ms = max_over_ranks(dist, [elapsed, timers[1] / max(timers[0], 1)])
     return {"k": k, "p": p, "m": m, "out": out, "elapsed": elapsed, "spmv_avg_ms": spmv_avg_ms,
             "timers": timers, "other_ms": other_ms, "normest_ms": normest_ms, "bytes": tbytes, "blocks": blocks, "solve_q_ms": solve_q_ms,
-            "K": K}
+            "K": K, "last_timed_out": last}
 
 
 def irl_roofline(M):
@@ -1216,12 +1332,12 @@ def main_irl(args, wd=None):
     s = args.s
     ml, nw = (int(x) for x in args.irl.split(","))
     r_full = np.random.RandomState(5489).random_sample(n)
-    K, W = max(1, min(args.steps, 5)), max(0, min(args.warmup, 1))
-    M = irl_measure(cal, ctx, r_full[r0:r1], ml, nw, s, args.basis, args.irl_tol, K, W, dist)
+    K, W = args.steps, args.warmup
+    M = irl_measure(cal, ctx, r_full[r0:r1], ml, nw, s, args.basis, args.irl_tol, K, W, dist, full=args.full)
     k, m, out = M["k"], M["m"], M["out"]
-    elapsed, spmv_avg_ms = M["elapsed"], M["spmv_avg_ms"]
-    spmv_cnt, spmv_ms, gram_cnt, gram_ms, apply_cnt, apply_ms = M["timers"]
-    blocks, solve_q_ms = M["blocks"], M["solve_q_ms"]
+    elapsed, blocks = M["elapsed"], M["blocks"]
+    if args.dump_outputs and rank == 0:
+        dump_irl(M.get("last_timed_out", out), args.dump_outputs)
     if wd is not None:
         wd.enter("finalize", stage_limit("finalize"))
     if rank != 0:
@@ -1230,9 +1346,6 @@ def main_irl(args, wd=None):
             wd.done()
         return
     fmt, _, _ = ctx.spmv_format()
-    n_loc = r1 - r0
-    b_spmv = (12 * nnz_local + 20 * n_loc + 4) if fmt == "csr" else 18 * n_loc
-    achieved = b_spmv / (spmv_avg_ms * 1e-3) / 1e9
     line = {
         "metric": "impl_restarted_ca_lanczos solves/sec (BASELINE config 5)",
         "value": K / elapsed,
@@ -1254,8 +1367,30 @@ def main_irl(args, wd=None):
         "converged": out["converged"],
         "top_eigs": [float(x) for x in out["conv_eigs"][:3]],
         "blocks_per_s": blocks / elapsed,
-        "solve_with_q_conv_download_ms": solve_q_ms,
         "spmv_format": fmt,
+    }
+    if args.full:
+        full_irl_line(args, E, M, line)
+    emit(line)
+    if dist is not None:
+        dist.barrier()
+    if wd is not None:
+        wd.done()
+
+
+def full_irl_line(args, E, M, line):
+    """--full of the IRL driver: the event-timed solve's per-kernel figures
+    and rooflines, the solve that downloads Q_conv and the CPU baseline."""
+    world, wl = E["world"], E["wl"]
+    nnz_local, n_loc = E["nnz_local"], E["r1"] - E["r0"]
+    ml, nw = (int(x) for x in args.irl.split(","))
+    spmv_avg_ms = M["spmv_avg_ms"]
+    spmv_cnt, spmv_ms, gram_cnt, gram_ms, apply_cnt, apply_ms = M["timers"]
+    fmt = line["spmv_format"]
+    b_spmv = (12 * nnz_local + 20 * n_loc + 4) if fmt == "csr" else 18 * n_loc
+    achieved = b_spmv / (spmv_avg_ms * 1e-3) / 1e9
+    line.update({
+        "solve_with_q_conv_download_ms": M["solve_q_ms"],
         "kernel_ms_per_solve": {"spmv": spmv_ms, "gram": gram_ms, "apply": apply_ms, "other": M["other_ms"]},
         "kernel_launches_per_solve": {"spmv": spmv_cnt, "gram": gram_cnt, "apply": apply_cnt},
         "roofline": dict(irl_roofline(M)[0], traffic=None),
@@ -1264,15 +1399,10 @@ def main_irl(args, wd=None):
                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_for(args, wl, world, "spmv"),
                           "kernel": "SpMV (%s) inside the IRL" % fmt, "bytes_per_launch": b_spmv,
                           "avg_launch_us": spmv_avg_ms * 1e3},
-    }
+    })
     line["host"] = host_info()
     if world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline_irl(wl, s, ml, nw)
-    emit(line)
-    if dist is not None:
-        dist.barrier()
-    if wd is not None:
-        wd.done()
+        line["cpu_baseline"] = cpu_baseline_irl(wl, args.s, ml, nw)
 
 
 if __name__ == "__main__":

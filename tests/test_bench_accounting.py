@@ -56,3 +56,31 @@ def test_restart_spread_fixture():
     assert len(c) == 98 and c.min() >= 80 and c.max() <= 170
     lo, hi = np.percentile(c, [10, 90])
     assert 90 <= lo <= np.median(c) <= hi <= 125
+
+
+def test_bench_dump_outputs_samples_a_large_block(tmp_path):
+    """Beyond its byte budget the last block of Q is dumped as a sorted row
+    sample that depends on the size alone."""
+    import numpy as np
+
+    class Ctx:
+        n = 2 * bench.DUMP_Q_BYTES // 64
+
+        def lanczos_state(self):
+            return 3, 8, 0
+
+        def lanczos_get(self):
+            return np.eye(24), None, None, np.zeros(3, dtype=np.int32), None
+
+        def lanczos_get_Q(self, col0, ncols):
+            assert 17 <= col0 <= 24 and ncols == 1
+            return (np.arange(self.n, dtype=np.float64) + col0 * 1e9).reshape(-1, 1)
+
+    d = str(tmp_path / "dump")
+    bench.dump_lanczos(Ctx(), d)
+    rows, Q = np.load(os.path.join(d, "Q_last_block_rows.npy")), np.load(os.path.join(d, "Q_last_block.npy"))
+    total = sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+    assert total <= 64 * 1000 * 1000
+    assert Q.shape == (bench.DUMP_Q_BYTES // 64, 8) and np.all(np.diff(rows) > 0) and rows[-1] < Ctx.n
+    assert np.array_equal(Q[:, 3], rows + 20e9)
+    assert np.array_equal(rows, np.sort(np.random.RandomState(bench.DUMP_SEED).choice(Ctx.n, len(rows), replace=False)))

@@ -1,6 +1,7 @@
 """bench.py's output contract, on a small workload: one JSON line on stdout
-with the fields the driver reads, the roofline and CPU-baseline objects, and
-the epoch path that keeps long runs inside the basis budget."""
+with the fields the driver reads, the headline-only plain run and its
+--dump-outputs, the roofline and CPU-baseline objects of --full, and the
+epoch path that keeps long runs inside the basis budget."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ def _bench(*args, timeout=240):
 
 
 def test_bench_contract_fields():
-    d = _bench("--workload", "lap3d_40", "--steps", "3", "--warmup", "1", "--cpu-iters", "2")
+    d = _bench("--full", "--workload", "lap3d_40", "--steps", "3", "--warmup", "1", "--cpu-iters", "2")
     assert d["metric"].startswith("CA-Lanczos outer-iters/sec") and d["unit"] == "outer-iters/s"
     assert d["value"] > 0 and d["ms_per_step"] > 0
     assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
@@ -45,6 +46,44 @@ def test_bench_contract_fields():
     irl = d["irl"]
     assert irl["converged"] and irl["solves_per_s"] > 0 and irl["spmv_format"] == "csr"
     assert 0 < irl["roofline"]["frac"] < 1.5
+
+
+FULL_ONLY = ("roofline", "kernel_ms_per_step", "cpu_baseline", "cpu_baseline_numpy", "diagnostics_on", "tsqr_step",
+             "csr_step", "full_step", "lap2d_3162_step", "lap2d_1000_step", "irl", "spmv_csr_kernel",
+             "spmv_kernel_back_to_back", "spmv_host_roundtrip_ms", "gram_mfma")
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """Without --full the line holds the headline of the timed steps and none
+    of the legs, per-kernel figures or baselines; --steps sets the number of
+    timed steps; --dump-outputs writes the last timed step's T, flags and
+    block of Q as float64 .npy, identical from run to run."""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        d = _bench("--gpus", "1", "--workload", "lap3d_40", "--steps", "4", "--warmup", "1", "--dump-outputs",
+                   str(tmp_path / tag))
+        assert d["metric"].startswith("CA-Lanczos outer-iters/sec") and d["unit"] == "outer-iters/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert (d["n_gpus"], d["steps"], d["warmup"]) == (1, 4, 1)
+        assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+        assert d["reorth_passes"].endswith("/4") and d["config"]["workload"].startswith("lap3d_40")
+        assert not set(FULL_ONLY) & set(d), sorted(set(FULL_ONLY) & set(d))
+        out = {f[:-4]: np.load(str(tmp_path / tag / f)) for f in sorted(os.listdir(str(tmp_path / tag)))}
+        assert set(out) == {"T", "reorth_flags", "Q_last_block", "Q_last_block_rows"}
+        assert all(a.dtype == np.float64 for a in out.values())
+        assert sum(a.nbytes for a in out.values()) <= 64 * 1000 * 1000
+        runs.append(out)
+    a, b = runs
+    # 1 warm-up + 4 timed outer iterations of s = 8: T is 40 x 40, the last block 8 columns of all 40^3 rows
+    assert a["T"].shape == (40, 40) and a["Q_last_block"].shape == (64000, 8) and a["reorth_flags"].shape == (5,)
+    assert np.array_equal(a["Q_last_block_rows"], np.arange(64000.0))
+    assert np.all(np.isfinite(a["T"])) and np.all(np.isfinite(a["Q_last_block"]))
+    # the block is orthonormal (CholQR2 / TSQR normalize): what the step is for
+    # (n eps: the worst-case rounding of an inner product of n = 40^3 terms)
+    assert np.max(np.abs(a["Q_last_block"].T @ a["Q_last_block"] - np.eye(8))) < 64000 * np.finfo(float).eps
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 def test_bench_epochs_keep_the_line_valid():
@@ -82,7 +121,7 @@ def test_bench_gpus_flag_launches_ranks():
     starts the two ranks itself -- it must not silently measure one GPU.
     Host-staged communicator: both ranks share the test box's GPU.  The TSQR
     leg runs on both ranks (its tree's root all-gathered)."""
-    d = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "lap3d_40", "--comm", "host",
+    d = _bench("--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "lap3d_40", "--comm", "host",
                timeout=300)
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["parallelism"] == "row-slab x2"
     assert d["config"]["comm"] == "host" and "cpu_baseline" not in d
@@ -97,9 +136,9 @@ def test_bench_gpus_flag_rccl_line():
     over RCCL's socket transport.  One line, the RCCL communicator counted on
     every rank, all-reduces and the one deep halo exchange per step."""
     env = dict(os.environ, CAL_RCCL_HOSTID_PER_RANK="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup",
-                        "1", "--workload", "lap3d_40"], cwd=ROOT, env=env, capture_output=True, text=True,
-                       timeout=300)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3",
+                        "--warmup", "1", "--workload", "lap3d_40"], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -119,7 +119,7 @@ def test_bench_matrix_file_both_drivers(cal, tmp_path):
     driver and the CA-Lanczos driver each print one valid line on the
     file's matrix."""
     _, p = _ingest(cal, tmp_path, "circuit_200", "mtx")
-    d = _bench("--matrix", p, "--driver", "irl", "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    d = _bench("--full", "--matrix", p, "--driver", "irl", "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
     assert d["metric"].startswith("impl_restarted_ca_lanczos solves/sec") and d["unit"] == "solves/s"
     assert d["config"]["workload"].startswith("file:circuit_200.mtx, n=40000")
     assert d["converged"] and d["value"] > 0 and d["steps"] == 2

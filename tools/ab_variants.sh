@@ -8,7 +8,7 @@ mkdir -p $O
 for rep in $(seq 1 ${REPS:-2}); do
 for v in $VARIANTS; do
     if [ "$v" = base ]; then L=""; else L="variant_$v"; fi
-    CAL_LIBRARY=$L timeout -k 10 300 python bench.py --no-cpu-baseline --no-legs --steps ${STEPS:-20} $BENCH_ARGS > $O/$v.$rep.json 2> $O/$v.$rep.err || exit $?
+    CAL_LIBRARY=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-legs --steps ${STEPS:-20} $BENCH_ARGS > $O/$v.$rep.json 2> $O/$v.$rep.err || exit $?
     python3 -c "
 import json; d=json.load(open('$O/$v.$rep.json'))
 ks = d.get('kernel_ms_per_step') or d.get('kernel_ms_per_solve') or {}

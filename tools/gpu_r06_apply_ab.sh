@@ -17,7 +17,7 @@ done
 for rep in 1 2; do
 for v in $VARIANTS; do
   if [ "$v" = base ]; then L=""; else L="variant_$v"; fi
-  CAL_LIBRARY=$L timeout -k 10 300 python bench.py --driver irl --no-cpu-baseline --steps 5 > $O/irl_$v.$rep.json 2> $O/irl_$v.$rep.err || exit $?
+  CAL_LIBRARY=$L timeout -k 10 300 python bench.py --full --driver irl --no-cpu-baseline --steps 5 > $O/irl_$v.$rep.json 2> $O/irl_$v.$rep.err || exit $?
   python3 -c "
 import json; d=json.load(open('$O/irl_$v.$rep.json')); print('%-8s irl %.2f' % ('$v', d['value']))"
 done

@@ -1,6 +1,7 @@
 # Round 6 verification: (PART=tests) the full GPU suite and smoke(); (PART=bench) the default
 # bench line and a rocprofv3 kernel-trace/stats run of the headline (no legs, no CPU baseline).
 set -o pipefail
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py  # the benchmark beside this folder
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/${TAG:-r06_bench}
 mkdir -p $O
@@ -11,7 +12,7 @@ if [ "$PART" = tests ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
   rc=$?; tail -2 $O/smoke.log; exit $rc
 fi
-timeout -k 10 700 python bench.py > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 700 python bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 python3 - <<PY
 import json
 d=json.load(open('$O/bench.json'))
@@ -22,5 +23,5 @@ print('irl', round(d['irl']['solves_per_s'],2), d['irl']['roofline']['kernel_cla
 print('diag', round(d['diagnostics_on']['outer_iters_per_s'],1), 'cpu', d['cpu_baseline']['value'], d['cpu_baseline'].get('min'), d['cpu_baseline'].get('max'))
 PY
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-legs > $O/bench_prof.json 2> $O/bench_prof.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $BENCH --full --no-cpu-baseline --no-legs > $O/bench_prof.json 2> $O/bench_prof.err
 echo "prof rc=$?"

@@ -6,5 +6,5 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06/${TAG:-host_trace}
 mkdir -p $O
-timeout -k 10 400 rocprofv3 --kernel-trace --hip-runtime-trace --output-format csv -d $O/prof -o run -- python3 bench.py --no-cpu-baseline --no-legs --steps 20 > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 400 rocprofv3 --kernel-trace --hip-runtime-trace --output-format csv -d $O/prof -o run -- python3 bench.py --full --no-cpu-baseline --no-legs --steps 20 > $O/bench.json 2> $O/bench.err || exit $?
 ls $O/prof

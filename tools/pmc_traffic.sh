@@ -2,6 +2,7 @@
 # counter group (MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE cannot share
 # a pass; no trace domains alongside --pmc).  Run on the GPU box:
 #   bash tools/pmc_traffic.sh            -> gpurun_out/pmc/<tag>_<group>/...
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py  # the benchmark beside this folder
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc
 mkdir -p $OUT
@@ -28,6 +29,6 @@ for grp in fetch write hit; do
     if [ -z "$BENCH_ONLY" ]; then
         run spmv $grp "${C[@]}" -- python3 $GRAFT_REPO_ROOT/tools/spmv_sweep.py --reps 10 || exit $?
     fi
-    run bench $grp "${C[@]}" -- python3 $GRAFT_REPO_ROOT/bench.py --steps $STEPS --warmup 1 --no-cpu-baseline $BENCH_ARGS || exit $?
+    run bench $grp "${C[@]}" -- python3 $BENCH --full --steps $STEPS --warmup 1 --no-cpu-baseline $BENCH_ARGS || exit $?
 done
 cd $GRAFT_REPO_ROOT && python3 tools/traffic_json.py gpurun_out/pmc --out gpurun_out/pmc/spmv_traffic.json > /dev/null
