@@ -3,21 +3,24 @@
 Drop-in for the reference's hot-path functions (SpMV.m,
 matrix_powers_{monomial,newton}.m, tsqr.m, cholqr.m, project.m,
 normalize.m, projectAndNormalize.m, ca_lanczos.m, restarted_ca_lanczos.m,
-impl_restarted_ca_lanczos.m) behind the C ABI of
+impl_restarted_ca_lanczos.m, ca_lanczos_prop.m) behind the C ABI of
 include/calanczos.h; see DESIGN.md and INTEGRATION.md.
 """
 from ._lib import CalError, LIB_PATH  # noqa: F401  (raises ImportError if the .so is missing)
 from .api import (  # noqa: F401
     CALanczosOutput,
     Context,
+    Propagator,
     SpMV,
     ca_lanczos,
     ca_lanczos_ex,
+    ca_lanczos_prop,
     cholqr,
     compute_ritz_rnorm,
     context_for,
     default_context,
     eig,
+    expm_col1,
     leja,
     matlab_rand,
     matrix_powers_monomial,

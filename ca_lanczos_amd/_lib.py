@@ -60,6 +60,14 @@ class RestartInfo(ctypes.Structure):
     ]
 
 
+class PropInfo(ctypes.Structure):
+    _fields_ = [
+        ("steps", c_int), ("lsteps", c_int), ("lsteps_max", c_int), ("lsteps_sum", ctypes.c_longlong),
+        ("residual", c_double), ("residual_max", c_double), ("norm", c_double),
+        ("nshifts", c_int), ("shifts", c_double * 64), ("breakdowns", c_int), ("rank_deficient", c_int), ("ms", c_double),
+    ]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, dp, c_int64)
 EXCHANGE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, dp, c_int64, dp, c_int64)
 
@@ -79,6 +87,7 @@ SIGNATURES = [
     ("cal_timer_reset", c_int, [c_void_p]),
     ("cal_set_matrix_csc", c_int, [c_void_p, c_int64, POINTER(c_int64), POINTER(c_int64), dp]),
     ("cal_set_matrix_csr", c_int, [c_void_p, c_int64, POINTER(c_int64), POINTER(c_int32), dp]),
+    ("cal_set_matrix_csr_stacked", c_int, [c_void_p, c_int64, POINTER(c_int64), POINTER(c_int32), dp]),
     ("cal_set_matrix_csr_dist", c_int,
      [c_void_p, c_int64, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), dp]),
     ("cal_matrix_info", c_int,
@@ -124,6 +133,13 @@ SIGNATURES = [
       POINTER(RestartInfo)]),
     ("cal_impl_restarted_ca_lanczos", c_int,
      [c_void_p, dp, c_int, c_int, c_int, c_char_p, c_char_p, c_double, dp, dp, dp, POINTER(RestartInfo)]),
+    ("cal_prop_combine", c_int, [c_void_p, c_int64, c_int, dp, dp, dp, dp, dp, dp]),
+    ("cal_prop_begin", c_int, [c_void_p, c_int64, dp, dp, c_int, c_int, c_char_p, dp, c_int]),
+    ("cal_prop_step", c_int, [c_void_p, c_double, c_double, c_int, c_int]),
+    ("cal_prop_get", c_int, [c_void_p, dp, dp, POINTER(PropInfo)]),
+    ("cal_prop_end", c_int, [c_void_p]),
+    ("cal_ca_lanczos_prop", c_int,
+     [c_void_p, c_int64, dp, dp, c_int, c_int, c_double, c_double, c_char_p, dp, c_int, c_int, dp, dp, dp, ip]),
     ("cal_comm_unique_id", c_int, [c_void_p]),
     ("cal_comm_init_rccl", c_int, [c_void_p, c_int, c_int, c_void_p]),
     ("cal_comm_init_host", c_int, [c_void_p, c_int, c_int, ALLREDUCE_FN, EXCHANGE_FN, c_void_p]),
@@ -135,6 +151,7 @@ SIGNATURES = [
     ("cal_matlab_rand", c_int, [c_int64, ctypes.c_uint, dp]),
     ("cal_tridiag_eigvals", c_int, [c_int, dp, dp, dp]),
     ("cal_qrstep", c_int, [c_int, dp, c_int, dp, c_int, c_double]),
+    ("cal_expm_col1", c_int, [c_int, dp, c_int, c_double, dp, dp]),
 ]
 
 for _name, _res, _args in SIGNATURES:

@@ -163,6 +163,35 @@ class Context:
         self.n = A.shape[0]
         return self
 
+    def set_matrix_stacked(self, H):
+        """blkdiag(H, H) through cal_set_matrix_csr_stacked: the real form of
+        a complex problem on stacked vectors [Re; Im] (the time propagator)."""
+        H = to_csr(H)
+        if H.shape[0] != H.shape[1]:
+            raise ValueError("H must be square")
+        rowptr = np.ascontiguousarray(H.indptr, dtype=np.int64)
+        col = np.ascontiguousarray(H.indices, dtype=np.int32)
+        val = np.ascontiguousarray(H.data, dtype=np.float64)
+        check(self.h, lib.cal_set_matrix_csr_stacked(
+            self.h, H.shape[0], rowptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            col.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(val)), "set_matrix_stacked")
+        self.n = 2 * H.shape[0]
+        return self
+
+    def prop_combine(self, Q, c):
+        """``nrm * Q_c * c`` on stacked halves (cal_prop_combine): Q is
+        2n x m real, c complex with m entries; returns (complex n-vector,
+        sum |out|^2 as the kernel's block partials reduce it)."""
+        Q = f64(Q)
+        n, m = Q.shape[0] // 2, Q.shape[1]
+        c = np.asarray(c, dtype=np.complex128).ravel()
+        cre, cim = np.ascontiguousarray(c.real), np.ascontiguousarray(c.imag)
+        ore, oim = np.zeros(n), np.zeros(n)
+        n2 = ctypes.c_double()
+        check(self.h, lib.cal_prop_combine(self.h, n, m, ptr(Q), ptr(cre), ptr(cim), ptr(ore), ptr(oim),
+                                           ctypes.cast(ctypes.byref(n2), dp)), "prop_combine")
+        return ore + 1j * oim, n2.value
+
     def set_matrix_csc(self, A):
         """MATLAB's sparse storage (mxGetJc / mxGetIr / mxGetPr: CSC with int64
         mwIndex arrays) through cal_set_matrix_csc, the entry a MEX shim uses."""
@@ -648,3 +677,116 @@ def impl_restarted_ca_lanczos(A, r, max_lanczos, n_wanted_eigs=10, s=6, basis="n
     return dict(conv_eigs=E[:k].copy(), Q_conv=V[:, :k].copy() if return_Q else None, num_restarts=nr,
                 ritz_est=est[:nr].copy(),
                 converged=bool(info.converged), norm_A=info.norm_A, ms=info.ms)
+
+
+# ---------------------------------------------------------------------------
+# Krylov time propagation psi(t+dt) = exp(-i dt H) psi(t)
+# ---------------------------------------------------------------------------
+def expm_col1(T, dt):
+    """``expm(-1i*dt*T)(:,1)`` for a general real square T (cal_expm_col1:
+    host only, ca_lanczos_prop.m:122)."""
+    T = f64(T)
+    m = T.shape[0]
+    cre, cim = np.zeros(max(m, 1)), np.zeros(max(m, 1))
+    st = lib.cal_expm_col1(m, ptr(T), max(m, 1), float(dt), ptr(cre), ptr(cim))
+    if st != 0:
+        raise CalError(st, "cal_expm_col1")
+    return cre[:m] + 1j * cim[:m]
+
+
+def _split(psi):
+    psi = np.asarray(psi)
+    re = np.ascontiguousarray(psi.real, dtype=np.float64).ravel()
+    im = np.ascontiguousarray(psi.imag, dtype=np.float64).ravel() if np.iscomplexobj(psi) else None
+    return re, im
+
+
+def _eigest(eigest):
+    if eigest is None or len(eigest) == 0:
+        return None, 0
+    e = np.ascontiguousarray(np.real(np.asarray(eigest)), dtype=np.float64).ravel()
+    return e, len(e)
+
+
+class Propagator:
+    """Time stepper ``psi <- exp(-i dt H) psi`` for a real symmetric sparse H
+    and a complex state (cal_prop_*; ca_lanczos_prop.m as runLanczos.m:84-131
+    drives it).  H is embedded as blkdiag(H, H) and the state lives on the
+    device as [Re psi; Im psi]; ``state()`` is the only copy back."""
+
+    def __init__(self, H, psi0, s, max_blocks, basis="newton", eigest=None, ctx=None):
+        self.n = H.shape[0]
+        self._own = ctx is None
+        self.ctx = ctx or Context()
+        try:
+            self.ctx.set_matrix_stacked(H)
+            re, im = _split(psi0)
+            if re.shape[0] != self.n:
+                raise ValueError("psi0 must have H.shape[0] entries")
+            e, ne = _eigest(eigest)
+            check(self.ctx.h, lib.cal_prop_begin(self.ctx.h, self.n, ptr(re), ptr(im), s, max_blocks,
+                                                 basis.encode(), ptr(e), ne), "prop_begin")
+        except Exception:
+            if self._own:
+                self.ctx.close()
+            raise
+        self._open = True
+
+    def step(self, dt, nsteps=1, tol=1.0e-10, adaptive=False):
+        """nsteps time steps of size dt; returns the status (0, or
+        CAL_WARN_BREAKDOWN when a step's first block broke down)."""
+        return check(self.ctx.h, lib.cal_prop_step(self.ctx.h, float(dt), float(tol), 1 if adaptive else 0,
+                                                   int(nsteps)), "prop_step")
+
+    def state(self):
+        re, im = np.zeros(self.n), np.zeros(self.n)
+        check(self.ctx.h, lib.cal_prop_get(self.ctx.h, ptr(re), ptr(im), None), "prop_get")
+        return re + 1j * im
+
+    def info(self):
+        i = _lib.PropInfo()
+        check(self.ctx.h, lib.cal_prop_get(self.ctx.h, None, None, ctypes.byref(i)), "prop_get")
+        return dict(steps=i.steps, lsteps=i.lsteps, lsteps_max=i.lsteps_max, lsteps_sum=i.lsteps_sum,
+                    residual=i.residual, residual_max=i.residual_max, norm=i.norm,
+                    shifts=np.array(i.shifts[:i.nshifts]), breakdowns=i.breakdowns, rank_deficient=i.rank_deficient, ms=i.ms)
+
+    def close(self):
+        if getattr(self, "_open", False):
+            self._open = False
+            if self.ctx.h:
+                check(self.ctx.h, lib.cal_prop_end(self.ctx.h), "prop_end")
+            if self._own:
+                self.ctx.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ca_lanczos_prop(A, r0, s, m, dt, tol=1.0e-10, basis="newton", eigest=None, adaptive=False, ctx=None):
+    """``[T,Q,lsteps] = ca_lanczos_prop(A,r0,s,m,dt,tol,basis,eigest,adaptive)``
+    -- ca_lanczos_prop.m:3-135 for a real symmetric A and a real or complex
+    r0; Q is complex n x lsteps."""
+    n = A.shape[0]
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        ctx.set_matrix_stacked(A)
+        re, im = _split(r0)
+        if re.shape[0] != n:
+            raise ValueError("r0 must have A.shape[0] entries")
+        e, ne = _eigest(eigest)
+        cap = max(int(s) * int(m), 1)
+        T = np.zeros(cap * cap)
+        Qre, Qim = np.zeros((n, cap), order="F"), np.zeros((n, cap), order="F")
+        ls = ctypes.c_int()
+        check(ctx.h, lib.cal_ca_lanczos_prop(ctx.h, n, ptr(re), ptr(im), s, m, float(dt), float(tol),
+                                             basis.encode(), ptr(e), ne, 1 if adaptive else 0, ptr(T), ptr(Qre),
+                                             ptr(Qim), ctypes.byref(ls)), "ca_lanczos_prop")
+        k = ls.value
+        return T[:k * k].reshape(k, k, order="F").copy(), Qre[:, :k] + 1j * Qim[:, :k], k
+    finally:
+        if own:
+            ctx.close()

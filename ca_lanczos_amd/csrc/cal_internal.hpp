@@ -214,6 +214,7 @@ struct DevMatrix {
 
 struct Comm;  // comm.cpp
 struct LanczosState;  // lanczos.cpp
+struct PropState;     // prop.cpp
 
 // Launchers (kernels.hip).  All enqueue on `st` and return hipError_t.
 hipError_t launch_spmv(const SpmvArgs& a, hipStream_t st);
@@ -450,6 +451,20 @@ hipError_t launch_fold_root(const FoldArgs& a, const double* T1, const double* G
                             unsigned long long* hseq, unsigned long long seq, hipStream_t st);
 hipError_t launch_fold_down(const ColList& P, const OutList& Q, const FoldArgs& a, hipStream_t st);
 
+// ---- Krylov time propagation: the half-mixing combine (prop.hip) ----------
+// The state is one real vector of 2n rows, Re psi in [0, n), Im psi in
+// [n, 2n).  Q: m columns (leading dimension ld, column j at Q + j ld), a / b:
+// m device coefficients (Re / Im of nrm * expm(-i dt T) e_1):
+//   out[i]     = sum_j Q[i,j] a_j - Q[i+n,j] b_j
+//   out[i + n] = sum_j Q[i,j] b_j + Q[i+n,j] a_j      (0 <= i < n)
+// in the fixed order of DESIGN.md (one chain per output row, j ascending) and
+// partial[block] = the block's sum of out^2 (prop_combine_blocks(n) blocks;
+// launch_reduce gives the next step's squared norm).  m <= kPropMaxCols.
+constexpr int kPropMaxCols = 512;
+int prop_combine_blocks(int64_t n);
+hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
+                               double* out, double* partial, hipStream_t st);
+
 
 }  // namespace cal
 
@@ -489,6 +504,7 @@ struct cal_ctx {
     int64_t work_ld = 0;
 
     cal::LanczosState* lz = nullptr;
+    cal::PropState* prop = nullptr;  // the time propagator's state (prop.cpp)
     cal::Comm* comm = nullptr;
 
     bool timing = false;
@@ -649,6 +665,39 @@ int timer_begin(cal_ctx* c, int kind, double bytes = 0.0);
 int timer_begin_on(cal_ctx* c, int kind, hipStream_t st);
 void timer_end_on(cal_ctx* c, int idx, hipStream_t st);
 void timer_end(cal_ctx* c, int idx);
+
+// ---- the CA-Lanczos loop as prop.cpp drives it (lanczos.cpp) --------------
+// cal_lanczos_begin is lanczos_begin with a host start vector and nothing
+// else set.
+struct LanczosBegin {
+    const double* r_host = nullptr;  // the start vector: n rows on the host, or
+    const double* r_dev = nullptr;   // on the device (local origin; not a column of the run's Q / V)
+    double rr = -1.0;                // r'r of a device start vector when the caller has it (< 0: computed)
+    // Newton basis: these shifts (Leja order, at least s, real) with
+    // newton_basis_matrix(shifts, s, 0) instead of the prologue
+    const double* shifts = nullptr;
+    int nshifts = 0;
+    bool prologue_cgs = true;        // the prologue's lanczos(...,'full'); false: 'local'
+    // keep the current run's Q / V allocation when s, max_outer and the
+    // matrix's vector layout are unchanged (no hipMalloc, no memset: the pad
+    // rows stay zero from the first allocation, every other row is written
+    // before it is read)
+    bool reuse = false;
+};
+int lanczos_begin(cal_ctx* c, const LanczosBegin& in, int s, int max_outer, const char* basis, const char* orth);
+int lanczos_step(cal_ctx* c, int diagnostics);
+// the running state: T (ldt x ldt column-major, rows / columns [0, s k) and
+// the coupling T(s k, s k - 1) valid), b (k entries), Q's first column
+struct LanczosView {
+    int s, k, ldt;
+    const double* T;
+    const double* b;
+    const double* Q;  // column j at Q + j ld (local origin)
+    int64_t ld;
+    int n_rank_deficient;
+    const double* shifts;  // cal_lanczos_info::shifts
+};
+LanczosView lanczos_view(cal_ctx* c);
 
 // Device block operations (blockorth.cpp).  All matrices column-major; n is
 // the number of (local) rows of the panels.

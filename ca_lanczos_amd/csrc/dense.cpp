@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstring>
 #include <vector>
 
@@ -824,6 +825,95 @@ void matlab_rand(std::mt19937& g, int64_t count, double* out) {
         const uint32_t a = g() >> 5, b = g() >> 6;
         out[i] = (a * 67108864.0 + b) / 9007199254740992.0;
     }
+}
+
+// ---- first column of expm(-i dt T) (Krylov time propagation) --------------
+namespace {
+using cd = std::complex<double>;
+// a * b without the library's Inf/NaN recovery (plain products, unfused)
+inline cd cmul(const cd a, const cd b) {
+    return cd(a.real() * b.real() - a.imag() * b.imag(), a.real() * b.imag() + a.imag() * b.real());
+}
+// C = A B (m x m, column-major, ld m); zero entries of B are skipped: the
+// scaled T is block tridiagonal, so the Taylor terms cost m nnz(T) each
+void cmatmul(int m, const cd* A, const cd* B, cd* C) {
+    for (int j = 0; j < m; ++j) {
+        cd* cj = C + (size_t)j * m;
+        for (int i = 0; i < m; ++i) cj[i] = cd(0.0, 0.0);
+        for (int k = 0; k < m; ++k) {
+            const cd b = B[k + (size_t)j * m];
+            if (b.real() == 0.0 && b.imag() == 0.0) continue;
+            const cd* ak = A + (size_t)k * m;
+            for (int i = 0; i < m; ++i) cj[i] += cmul(ak[i], b);
+        }
+    }
+}
+double cnorm1(int m, const cd* A) {
+    double nrm = 0.0;
+    for (int j = 0; j < m; ++j) {
+        double cs = 0.0;
+        for (int i = 0; i < m; ++i) cs += std::abs(A[i + (size_t)j * m]);
+        nrm = std::max(nrm, cs);
+    }
+    return nrm;
+}
+}  // namespace
+
+bool expm_col1(int m, const double* T, int ldt, double dt, double* c_re, double* c_im) {
+    // scaling and squaring: A = -i dt T / 2^sq with ||A||_1 <= 1, the Taylor
+    // series of exp(A) to below the last bit, sq squarings (the last one
+    // applied to the first column only)
+    double nrm = 0.0;
+    for (int j = 0; j < m; ++j) {
+        double cs = 0.0;
+        for (int i = 0; i < m; ++i) cs += std::fabs(dt * T[i + (size_t)j * ldt]);
+        nrm = std::max(nrm, cs);
+    }
+    if (!std::isfinite(nrm)) return false;
+    int sq = 0;
+    if (nrm > 1.0) {
+        std::frexp(nrm, &sq);  // nrm = f 2^sq, f in [0.5, 1)
+        if (sq > 1000) return false;
+    }
+    const double scale = std::ldexp(1.0, -sq);
+    const size_t mm = (size_t)m * m;
+    std::vector<cd> A(mm), E(mm), P(mm), W(mm);
+    for (int j = 0; j < m; ++j)
+        for (int i = 0; i < m; ++i) {
+            const double x = dt * T[i + (size_t)j * ldt] * scale;
+            A[i + (size_t)j * m] = cd(0.0, x == 0.0 ? 0.0 : -x);
+        }
+    E = A;
+    for (int i = 0; i < m; ++i) E[i + (size_t)i * m] += cd(1.0, 0.0);
+    P = A;
+    for (int k = 2; k <= 64; ++k) {
+        cmatmul(m, P.data(), A.data(), W.data());
+        const double inv = 1.0 / k;
+        for (size_t e = 0; e < mm; ++e) {
+            W[e] = cd(W[e].real() * inv, W[e].imag() * inv);
+            E[e] += W[e];
+        }
+        P.swap(W);
+        if (cnorm1(m, P.data()) < 1e-22) break;
+    }
+    for (int q = 0; q + 1 < sq; ++q) {
+        cmatmul(m, E.data(), E.data(), W.data());
+        E.swap(W);
+    }
+    if (sq > 0) {  // c = E E(:,1)
+        for (int i = 0; i < m; ++i) W[i] = cd(0.0, 0.0);
+        for (int k = 0; k < m; ++k) {
+            const cd b = E[k];
+            const cd* ek = E.data() + (size_t)k * m;
+            for (int i = 0; i < m; ++i) W[i] += cmul(ek[i], b);
+        }
+        for (int i = 0; i < m; ++i) E[i] = W[i];
+    }
+    for (int i = 0; i < m; ++i) {
+        c_re[i] = E[i].real();
+        c_im[i] = E[i].imag();
+    }
+    return true;
 }
 
 }  // namespace dense

@@ -46,6 +46,9 @@ void hess_qrsteps(int m, double* H, int ldh, double* W, int ldw, const double* m
 // `count` draws of MATLAB's rand from the MT19937 stream g (genrand_res53:
 // two 32-bit words per double)
 void matlab_rand(std::mt19937& g, int64_t count, double* out);
+// c = expm(-i dt T) e_1 for a general real m x m T (scaling and squaring with
+// a Taylor series, complex arithmetic).  False when dt T is not finite.
+bool expm_col1(int m, const double* T, int ldt, double dt, double* c_re, double* c_im);
 
 }  // namespace dense
 }  // namespace cal

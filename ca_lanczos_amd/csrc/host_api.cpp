@@ -1,11 +1,12 @@
 // host_api.cpp -- the host-only entry points of calanczos_host.h (no HIP):
 // the T-matrix eigen-analysis (ca_lanczos.m:229), qrstep
-// (impl_restarted_ca_lanczos.m:623-678), the prologue's tridiagonal eig and
-// MATLAB's rand.  Built into libcalanczos.so with the rest, and on its own
+// (impl_restarted_ca_lanczos.m:623-678), the prologue's tridiagonal eig,
+// MATLAB's rand and the time propagator's expm(-i dt T) e_1.  Built into libcalanczos.so with the rest, and on its own
 // with g++ -fsanitize=address,undefined into the host checker
 // (csrc/Makefile `host-san`, tests/test_host_sanitized.py), together with
 // dense.cpp, leja.cpp and the TSQR tree plan.
 #include <atomic>
+#include <cmath>
 #include <random>
 
 #include "../../include/calanczos_host.h"
@@ -49,6 +50,12 @@ int cal_matlab_rand(int64_t count, unsigned seed, double* out) {
     std::mt19937 g(seed);
     dense::matlab_rand(g, count, out);
     return 0;
+}
+
+// c = expm(-i dt T) e_1 (ca_lanczos_prop.m:122, runLanczos.m:102-103)
+int cal_expm_col1(int m, const double* T, int ldt, double dt, double* c_re, double* c_im) {
+    if (m < 1 || m > 512 || !T || ldt < m || !c_re || !c_im || !std::isfinite(dt)) return CAL_ERR_ARG;
+    return dense::expm_col1(m, T, ldt, dt, c_re, c_im) ? 0 : CAL_ERR_NUMERIC;
 }
 
 static std::atomic<long long> g_residency_gen{0};

@@ -1400,10 +1400,15 @@ void cal_lanczos_free_state(cal_ctx* c) {
     c->lz = nullptr;
 }
 
-int cal_lanczos_begin(cal_ctx* c, const double* r, int s, int max_outer, const char* basis, const char* orth) {
+}  // extern "C"
+
+namespace cal {
+
+int lanczos_begin(cal_ctx* c, const LanczosBegin& in, int s, int max_outer, const char* basis, const char* orth) {
     if (!c) return CAL_ERR_ARG;
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
-    if (!r || s < 1 || s > kMaxS || max_outer < 1 || !basis)
+    const bool have_r = in.r_host || in.r_dev;
+    if (!have_r || s < 1 || s > kMaxS || max_outer < 1 || !basis)
         return set_error(c, CAL_ERR_ARG, "cal_lanczos_begin: need r, 1 <= s <= 31, max_outer >= 1");
     std::string o = orth ? orth : "local", b = basis;
     for (auto& ch : o) ch = (char)tolower(ch);
@@ -1411,7 +1416,15 @@ int cal_lanczos_begin(cal_ctx* c, const double* r, int s, int max_outer, const c
     if (o != "local" && o != "full" && o != "periodic" && o != "selective")
         return set_error(c, CAL_ERR_ARG, "ca_lanczos.m: Invalid option value for orth: " + o);
     if (b != "monomial" && b != "newton") return set_error(c, CAL_ERR_ARG, "ERROR: Unknown basis type: " + b);
+    if (in.shifts && in.nshifts < s) return set_error(c, CAL_ERR_ARG, "lanczos_begin: fewer than s Newton shifts");
     hipSetDevice(c->device);
+    // the previous run's Q / V buffers, kept when the shapes match
+    double *keepQ = nullptr, *keepV = nullptr;
+    if (in.reuse && c->lz && c->lz->s == s && c->lz->max_outer == max_outer && c->lz->ld == c->A.ld &&
+        c->lz->lpad == c->A.lpad && c->lz->n == c->A.n_local && c->lz->dQ && c->lz->dV) {
+        std::swap(keepQ, c->lz->dQ);
+        std::swap(keepV, c->lz->dV);
+    }
     cal_lanczos_free_state(c);
 #ifdef CAL_TEST_HOOKS
     c->test_R1.clear();
@@ -1428,10 +1441,15 @@ int cal_lanczos_begin(cal_ctx* c, const double* r, int s, int max_outer, const c
     L->lpad = c->A.lpad;
     L->info.s = s;
     const size_t qcols = (size_t)s * max_outer + 1;
-    CAL_HIP(c, hipMalloc((void**)&L->dQ, qcols * L->ld * sizeof(double)));
-    CAL_HIP(c, hipMalloc((void**)&L->dV, (size_t)2 * (s + 1) * L->ld * sizeof(double)));
-    CAL_HIP(c, hipMemsetAsync(L->dQ, 0, qcols * L->ld * sizeof(double), c->stream));
-    CAL_HIP(c, hipMemsetAsync(L->dV, 0, (size_t)2 * (s + 1) * L->ld * sizeof(double), c->stream));
+    if (keepQ) {
+        L->dQ = keepQ;
+        L->dV = keepV;
+    } else {
+        CAL_HIP(c, hipMalloc((void**)&L->dQ, qcols * L->ld * sizeof(double)));
+        CAL_HIP(c, hipMalloc((void**)&L->dV, (size_t)2 * (s + 1) * L->ld * sizeof(double)));
+        CAL_HIP(c, hipMemsetAsync(L->dQ, 0, qcols * L->ld * sizeof(double), c->stream));
+        CAL_HIP(c, hipMemsetAsync(L->dV, 0, (size_t)2 * (s + 1) * L->ld * sizeof(double), c->stream));
+    }
     L->Tld = s * max_outer + 1;
     L->T.assign((size_t)L->Tld * L->Tld, 0.0);
     {
@@ -1443,12 +1461,24 @@ int cal_lanczos_begin(cal_ctx* c, const double* r, int s, int max_outer, const c
     }
     const double t0 = now_ms();
     // q = r/sqrt(r'*r) (ca_lanczos.m:55)
-    CAL_HIP(c, hipMemcpyAsync(L->vcolumn(0), r, L->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    double rr = 0.0;
-    CAL_TRY(dot_host(c, L->n, L->vcolumn(0), L->vcolumn(0), &rr));
-    CAL_HIP_OTHER(c, launch_div(L->col(0), L->vcolumn(0), std::sqrt(rr), L->n, c->stream));
-    if (L->newton) {
-        CAL_TRY(newton_prologue(c, *L));
+    const double* r = in.r_dev;
+    if (in.r_host) {
+        CAL_HIP(c, hipMemcpyAsync(L->vcolumn(0), in.r_host, L->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        r = L->vcolumn(0);
+    }
+    double rr = in.rr;
+    if (in.r_host || !(rr >= 0.0)) CAL_TRY(dot_host(c, L->n, r, r, &rr));
+    CAL_HIP_OTHER(c, launch_div(L->col(0), r, std::sqrt(rr), L->n, c->stream));
+    if (L->newton && in.shifts) {
+        // basis_shifts handed over: Bk = newton_basis_matrix(shifts, s, 0) (ca_lanczos_prop.m:38-41)
+        std::vector<std::complex<double>> y(in.nshifts);
+        for (int i = 0; i < in.nshifts; ++i) y[i] = std::complex<double>(in.shifts[i], 0.0);
+        for (int i = 0; i < in.nshifts && i < 64; ++i) L->info.shifts[i] = in.shifts[i];
+        std::string err;
+        if (leja::newton_basis_matrix(s, y, 0, L->Bk, err) != 0)
+            return set_error(c, CAL_ERR_NUMERIC, "newton_basis_matrix: " + err);
+    } else if (L->newton) {
+        CAL_TRY(newton_prologue(c, *L, in.prologue_cgs));
     } else {  // Bk = I(:,2:s+1) (ca_lanczos.m:63-65)
         L->Bk.assign((size_t)(s + 1) * s, 0.0);
         for (int j = 0; j < s; ++j) L->Bk[(j + 1) + (size_t)j * (s + 1)] = 1.0;
@@ -1458,6 +1488,22 @@ int cal_lanczos_begin(cal_ctx* c, const double* r, int s, int max_outer, const c
     CAL_HIP(c, hipStreamSynchronize(c->stream));
     L->info.prologue_ms = now_ms() - t0;
     return 0;
+}
+
+LanczosView lanczos_view(cal_ctx* c) {
+    LanczosState& L = *c->lz;
+    return LanczosView{L.s, L.k, L.Tld, L.T.data(), L.b.data(), L.col(0), L.ld, L.info.n_rank_deficient,
+                       L.info.shifts};
+}
+
+}  // namespace cal
+
+extern "C" {
+
+int cal_lanczos_begin(cal_ctx* c, const double* r, int s, int max_outer, const char* basis, const char* orth) {
+    LanczosBegin in;
+    in.r_host = r;
+    return lanczos_begin(c, in, s, max_outer, basis, orth);
 }
 
 int cal_lanczos_step(cal_ctx* c, int diagnostics) {

@@ -1,0 +1,388 @@
+// prop.cpp -- Krylov time propagation psi(t+dt) = exp(-i dt H) psi(t) on the
+// CA-Lanczos basis (ca_lanczos_prop.m:3-135 as runLanczos.m:84-131 drives it).
+//
+// H is real symmetric and psi = u + i v complex.  Hermitian Lanczos on psi
+// has real recurrence coefficients, so q_j = p_j(H) u + i p_j(H) v with real
+// polynomials p_j: exactly real Lanczos on blkdiag(H, H) from the stacked
+// vector [u; v].  The context's matrix is that 2n x 2n embedding
+// (cal_set_matrix_csr_stacked), the state one real device vector of 2n rows
+// (Re in [0, n), Im in [n, 2n)), and a time step is
+//   normalise -> CA blocks ('local', lanczos_step unchanged) -> after block k
+//   c = expm(-i dt T(1:ks,1:ks)) e_1 on the host and the reference's residual
+//   |dt b(k) c(ks) nrm| (:122-123) -> psi <- nrm Q_c c (prop.hip, which also
+//   leaves the new squared norm).
+// The state, Q and the norm stay on the device across steps; the Lanczos
+// run's Q / V allocation is reused, and the Newton shifts of the first step
+// serve every later one (runLanczos.m:93-96 passes eigest the same way).
+// The one deliberate difference from ca_lanczos_prop.m: :78 projects with
+// doreorth = false, the blocks here apply the library's second-pass rule
+// (projectAndNormalize's 'second'), which is at least as orthogonal.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <complex>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../include/calanczos_host.h"
+#include "cal_internal.hpp"
+#include "comm.hpp"
+#include "dense.hpp"
+#include "leja.hpp"
+
+namespace cal {
+
+struct PropState {
+    int64_t n = 0;        // rows of H (the matrix has 2n)
+    int s = 0, max_blocks = 0;
+    bool newton = false;
+    bool have_shifts = false;
+    std::vector<double> shifts;  // Leja order
+    double* d_psi = nullptr;     // one vector column (A.ld doubles, local origin at +lpad)
+    double* d_coef = nullptr;    // a (kPropMaxCols) then b
+    double* h_coef = nullptr;    // pinned; [2 kPropMaxCols] receives the squared norm
+    double nrm2 = 0.0;           // psi'psi
+    cal_prop_info info{};
+    double* psi(const cal_ctx* c) const { return d_psi + c->A.lpad; }
+};
+
+namespace {
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+void prop_free(cal_ctx* c) {
+    if (!c || !c->prop) return;
+    if (c->prop->d_psi) hipFree(c->prop->d_psi);
+    if (c->prop->d_coef) hipFree(c->prop->d_coef);
+    if (c->prop->h_coef) hipHostFree(c->prop->h_coef);
+    delete c->prop;
+    c->prop = nullptr;
+}
+
+// psi <- Q(:, 0:m) (a + i b) and nrm2 <- psi'psi (a, b: Re / Im of nrm c, on the host)
+int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, const double* a, const double* b) {
+    std::memcpy(P.h_coef, a, m * sizeof(double));
+    std::memcpy(P.h_coef + kPropMaxCols, b, m * sizeof(double));
+    CAL_HIP_OTHER(c, hipMemcpyAsync(P.d_coef, P.h_coef, 2 * kPropMaxCols * sizeof(double), hipMemcpyHostToDevice,
+                                    c->stream));
+    const int nb = prop_combine_blocks(P.n);
+    CAL_TRY(ensure_partial(c, nb));
+    CAL_TRY(ensure_red(c, 1));
+    const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n) * 8.0);
+    const hipError_t e =
+        launch_prop_combine(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c), c->d_partial, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1, c->d_red, c->stream));
+    CAL_HIP_OTHER(c, hipMemcpyAsync(P.h_coef + 2 * kPropMaxCols, c->d_red, sizeof(double), hipMemcpyDeviceToHost,
+                                    c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    P.nrm2 = P.h_coef[2 * kPropMaxCols];
+    return 0;
+}
+
+// One Krylov build from the current state: CA blocks until max_blocks, the
+// adaptive stop or a dropped block.  *kuse blocks are usable (0: the first
+// block broke down); cre / cim: expm(-i dt T(1:ks,1:ks)) e_1 for ks = s kuse.
+int krylov(cal_ctx* c, PropState& P, double dt, double tol, int adaptive, int* kuse, std::vector<double>& cre,
+           std::vector<double>& cim, double* resid) {
+    const int s = P.s;
+    const double nrm = std::sqrt(P.nrm2);
+    LanczosBegin in;
+    in.r_dev = P.psi(c);
+    in.rr = P.nrm2;
+    in.prologue_cgs = false;  // lanczos(A,r0,2*s,'local') (ca_lanczos_prop.m:33)
+    in.reuse = true;
+    if (P.newton && P.have_shifts) {
+        in.shifts = P.shifts.data();
+        in.nshifts = (int)P.shifts.size();
+    }
+    CAL_TRY(lanczos_begin(c, in, s, P.max_blocks, P.newton ? "newton" : "monomial", "local"));
+    if (P.newton && !P.have_shifts) {  // the prologue's shifts serve every later step
+        const LanczosView v = lanczos_view(c);
+        P.shifts.assign(v.shifts, v.shifts + std::min(2 * s, 64));
+        P.have_shifts = true;
+    }
+    *kuse = 0;
+    std::vector<double> tre((size_t)s * P.max_blocks), tim((size_t)s * P.max_blocks);
+    for (int k = 1; k <= P.max_blocks; ++k) {
+        const int rd0 = lanczos_view(c).n_rank_deficient;
+        const int st = lanczos_step(c, 0);
+        if (st < 0) return st;
+        const LanczosView v = lanczos_view(c);
+        if (st == CAL_WARN_BREAKDOWN) {  // rho_t == 0 or a non-finite T: the block is dropped
+            P.info.breakdowns++;
+            break;
+        }
+        // normalize's 'Rank deficient' (svd(R) against 1e-8 s_1): the reference
+        // displays it and goes on (normalize.m:21-27), and so does this loop --
+        // a smooth state's first block is flagged routinely (the oscillator's
+        // Krylov basis has kappa > 1e8) while its T still propagates within
+        // the bar; the residual below judges the block
+        P.info.rank_deficient += v.n_rank_deficient - rd0;
+        const int ks = k * s;
+        double r = std::numeric_limits<double>::quiet_NaN();
+        if (dense::expm_col1(ks, v.T, v.ldt, dt, tre.data(), tim.data()))
+            r = std::fabs(dt * v.b[k - 1] * nrm) * std::hypot(tre[ks - 1], tim[ks - 1]);  // :123
+        if (!std::isfinite(r)) {  // a non-finite T: the block is dropped like a breakdown
+            P.info.breakdowns++;
+            break;
+        }
+        *kuse = k;
+        *resid = r;
+        cre.assign(tre.begin(), tre.begin() + ks);
+        cim.assign(tim.begin(), tim.begin() + ks);
+        if (adaptive && r < tol && ks >= 3) break;  // :124
+    }
+    return 0;
+}
+
+int check_prop_args(cal_ctx* c, int64_t n, int s, int max_blocks, const char* basis, bool* newton) {
+    if (!c) return CAL_ERR_ARG;
+    hipSetDevice(c->device);
+    if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    if (c->comm && c->comm->nranks > 1)
+        return set_error(c, CAL_ERR_UNSUPPORTED, "time propagation runs on one rank");
+    if (n < 1 || c->A.n_local != 2 * n)
+        return set_error(c, CAL_ERR_ARG, "cal_prop: the matrix must have 2n rows (cal_set_matrix_csr_stacked)");
+    if (s < 1 || s > 31 || max_blocks < 1 || (int64_t)s * max_blocks > kPropMaxCols)
+        return set_error(c, CAL_ERR_ARG, "cal_prop: need 1 <= s <= 31 and s*max_blocks <= 512");
+    std::string b = basis ? basis : "";
+    for (auto& ch : b) ch = (char)tolower(ch);
+    if (b != "monomial" && b != "newton") return set_error(c, CAL_ERR_ARG, "ERROR: Unknown basis type: " + b);
+    *newton = b == "newton";
+    return 0;
+}
+
+}  // namespace
+}  // namespace cal
+
+using namespace cal;
+
+extern "C" {
+
+void cal_prop_free_state(cal_ctx* c) { prop_free(c); }
+
+int cal_set_matrix_csr_stacked(cal_ctx* c, int64_t n, const int64_t* rowptr, const int32_t* colind,
+                               const double* val) {
+    if (!c || n < 0 || !rowptr || (n > 0 && rowptr[n] > 0 && (!colind || !val)))
+        return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csr_stacked: bad arguments");
+    const int64_t nnz = rowptr[n];
+    if (nnz < 0 || 2 * nnz >= ((int64_t)1 << 31) || 2 * n >= ((int64_t)1 << 31))
+        return set_error(c, CAL_ERR_UNSUPPORTED, "n and nnz must be < 2^31 per rank");
+    for (int64_t i = 0; i < n; ++i)
+        if (rowptr[i + 1] < rowptr[i]) return set_error(c, CAL_ERR_ARG, "row pointers must be non-decreasing");
+    std::vector<int64_t> rp(2 * n + 1);
+    std::vector<int32_t> col(2 * nnz);
+    std::vector<double> v(2 * nnz);
+    for (int64_t i = 0; i <= n; ++i) rp[i] = rowptr[i];
+    for (int64_t i = 1; i <= n; ++i) rp[n + i] = nnz + rowptr[i];
+    for (int64_t p = 0; p < nnz; ++p) {
+        if (colind[p] < 0 || colind[p] >= n) return set_error(c, CAL_ERR_ARG, "column index out of range");
+        col[p] = colind[p];
+        col[nnz + p] = (int32_t)(colind[p] + n);
+        v[p] = val[p];
+        v[nnz + p] = val[p];
+    }
+    return cal_set_matrix_csr(c, 2 * n, rp.data(), col.data(), v.data());
+}
+
+int cal_prop_combine(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
+                     double* out_re, double* out_im, double* norm2) {
+    if (!c) return CAL_ERR_ARG;
+    hipSetDevice(c->device);
+    if (n < 1 || m < 1 || m > kPropMaxCols || !Q || !c_re || !c_im || !out_re || !out_im)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_combine: need n >= 1, 1 <= m <= 512 and non-null arrays");
+    const int64_t ld = ((2 * n + 63) / 64) * 64;
+    const int nb = prop_combine_blocks(n);
+    // Q (ld x m), out (ld), the coefficients (2 m)
+    CAL_TRY(ensure_scratch(c, (size_t)ld * (m + 1) + 2 * (size_t)m));
+    CAL_TRY(ensure_partial(c, nb));
+    CAL_TRY(ensure_red(c, 1));
+    double* dQ = c->d_scratch;
+    double* dout = dQ + (size_t)ld * m;
+    double* dco = dout + ld;
+    CAL_HIP(c, hipMemcpy2DAsync(dQ, ld * sizeof(double), Q, 2 * n * sizeof(double), 2 * n * sizeof(double), m,
+                                hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco, c_re, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const int t = timer_begin(c, 2, ((double)2 * n * m + (double)2 * n) * 8.0);
+    const hipError_t e = launch_prop_combine(dQ, ld, n, m, dco, dco + m, dout, c->d_partial, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1, c->d_red, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out_re, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out_im, dout + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    double nn = 0.0;
+    CAL_HIP(c, hipMemcpyAsync(&nn, c->d_red, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    if (norm2) *norm2 = nn;
+    return 0;
+}
+
+static int prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* psi_im, int s, int max_blocks,
+                      const char* basis, const double* eigest, int neig) {
+    bool newton = false;
+    CAL_TRY(check_prop_args(c, n, s, max_blocks, basis, &newton));
+    if (!psi_re || neig < 0 || (neig > 0 && !eigest))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_begin: need psi_re (and eigest when neig > 0)");
+    prop_free(c);
+    PropState* P = new PropState();
+    c->prop = P;
+    P->n = n;
+    P->s = s;
+    P->max_blocks = max_blocks;
+    P->newton = newton;
+    if (newton && neig > 0) {
+        // basis_shifts = leja(real(eigest)) (ca_lanczos_prop.m:38-40)
+        if (neig < s) return set_error(c, CAL_ERR_ARG, "cal_prop_begin: fewer than s eigenvalue estimates");
+        std::vector<std::complex<double>> x(neig), y;
+        for (int i = 0; i < neig; ++i) {
+            if (!std::isfinite(eigest[i])) return set_error(c, CAL_ERR_ARG, "cal_prop_begin: non-finite eigest");
+            x[i] = std::complex<double>(eigest[i], 0.0);
+        }
+        std::vector<int> oi;
+        std::string err;
+        if (leja::real_leja(x, y, oi, err) != 0) return set_error(c, CAL_ERR_NUMERIC, "leja: " + err);
+        if ((int)y.size() < s) return set_error(c, CAL_ERR_ARG, "cal_prop_begin: fewer than s distinct estimates");
+        for (const auto& v : y) P->shifts.push_back(v.real());
+        P->have_shifts = true;
+    }
+    const int64_t ld = c->A.ld;
+    CAL_HIP(c, hipMalloc((void**)&P->d_psi, ld * sizeof(double)));
+    CAL_HIP(c, hipMalloc((void**)&P->d_coef, 2 * kPropMaxCols * sizeof(double)));
+    CAL_HIP(c, hipHostMalloc((void**)&P->h_coef, (2 * kPropMaxCols + 8) * sizeof(double), hipHostMallocDefault));
+    std::memset(P->h_coef, 0, (2 * kPropMaxCols + 8) * sizeof(double));
+    CAL_HIP(c, hipMemsetAsync(P->d_psi, 0, ld * sizeof(double), c->stream));
+    CAL_HIP(c, hipMemcpyAsync(P->psi(c), psi_re, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (psi_im)
+        CAL_HIP(c, hipMemcpyAsync(P->psi(c) + n, psi_im, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // the first norm: one sweep; every later one comes out of the combine
+    const int nb = dot_blocks(2 * n);
+    CAL_TRY(ensure_partial(c, nb));
+    CAL_TRY(ensure_red(c, 1));
+    CAL_HIP_OTHER(c, launch_dot(P->psi(c), P->psi(c), 2 * n, c->d_partial, nb, c->stream));
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1, c->d_red, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(P->h_coef + 2 * kPropMaxCols, c->d_red, sizeof(double), hipMemcpyDeviceToHost,
+                              c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    P->nrm2 = P->h_coef[2 * kPropMaxCols];
+    if (!(P->nrm2 > 0.0) || !std::isfinite(P->nrm2))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_begin: the start state must be finite and non-zero");
+    P->info.norm = std::sqrt(P->nrm2);
+    return 0;
+}
+
+int cal_prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* psi_im, int s, int max_blocks,
+                   const char* basis, const double* eigest, int neig) {
+    const int st = prop_begin(c, n, psi_re, psi_im, s, max_blocks, basis, eigest, neig);
+    if (st < 0 && c) prop_free(c);  // no half-built propagator is left behind
+    return st;
+}
+
+int cal_prop_step(cal_ctx* c, double dt, double tol, int adaptive, int nsteps) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_step: no active propagator");
+    hipSetDevice(c->device);
+    PropState& P = *c->prop;
+    if (!std::isfinite(dt) || nsteps < 0 || std::isnan(tol))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_step: need a finite dt, a tol and nsteps >= 0");
+    if (!c->has_A || c->A.n_local != 2 * P.n)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_step: the context's matrix changed since cal_prop_begin");
+    const double t0 = now_ms();
+    std::vector<double> cre, cim;
+    int status = 0;
+    for (int it = 0; it < nsteps; ++it) {
+        const double nrm = std::sqrt(P.nrm2);
+        int kuse = 0;
+        double resid = 0.0;
+        status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid);
+        if (status < 0) break;
+        if (kuse == 0) {  // the state is unchanged
+            status = set_error(c, CAL_WARN_BREAKDOWN, "cal_prop_step: the first CA block broke down");
+            break;
+        }
+        const int ks = kuse * P.s;
+        for (int j = 0; j < ks; ++j) {  // nrm * c
+            cre[j] = nrm * cre[j];
+            cim[j] = nrm * cim[j];
+        }
+        const LanczosView v = lanczos_view(c);
+        status = combine_dev(c, P, v.Q, v.ld, ks, cre.data(), cim.data());
+        if (status < 0) break;
+        P.info.steps++;
+        P.info.lsteps = ks;
+        P.info.lsteps_max = std::max(P.info.lsteps_max, ks);
+        P.info.lsteps_sum += ks;
+        P.info.residual = resid;
+        P.info.residual_max = std::max(P.info.residual_max, resid);
+        P.info.norm = std::sqrt(P.nrm2);
+    }
+    P.info.ms += now_ms() - t0;
+    return status;
+}
+
+int cal_prop_get(cal_ctx* c, double* psi_re, double* psi_im, cal_prop_info* info) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_get: no active propagator");
+    hipSetDevice(c->device);
+    PropState& P = *c->prop;
+    if (psi_re) CAL_HIP(c, hipMemcpyAsync(psi_re, P.psi(c), P.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (psi_im)
+        CAL_HIP(c, hipMemcpyAsync(psi_im, P.psi(c) + P.n, P.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (psi_re || psi_im) CAL_HIP(c, hipStreamSynchronize(c->stream));
+    if (info) {
+        *info = P.info;
+        info->nshifts = P.have_shifts ? (int)std::min<size_t>(P.shifts.size(), 64) : 0;
+        for (int i = 0; i < 64; ++i) info->shifts[i] = i < info->nshifts ? P.shifts[i] : 0.0;
+    }
+    return 0;
+}
+
+int cal_prop_end(cal_ctx* c) {
+    if (!c) return CAL_ERR_ARG;
+    hipSetDevice(c->device);
+    hipStreamSynchronize(c->stream);
+    prop_free(c);
+    cal_lanczos_end(c);
+    return 0;
+}
+
+int cal_ca_lanczos_prop(cal_ctx* c, int64_t n, const double* r_re, const double* r_im, int s, int m, double dt,
+                        double tol, const char* basis, const double* eigest, int neig, int adaptive, double* T,
+                        double* Q_re, double* Q_im, int* lsteps) {
+    if (!c) return CAL_ERR_ARG;
+    if (!T || !lsteps || !std::isfinite(dt) || std::isnan(tol))
+        return set_error(c, CAL_ERR_ARG, "cal_ca_lanczos_prop: need T, lsteps, a finite dt and a tol");
+    CAL_TRY(cal_prop_begin(c, n, r_re, r_im, s, m, basis, eigest, neig));
+    PropState& P = *c->prop;
+    std::vector<double> cre, cim;
+    int kuse = 0;
+    double resid = 0.0;
+    int status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid);
+    if (status >= 0 && kuse == 0)
+        status = set_error(c, CAL_WARN_BREAKDOWN, "cal_ca_lanczos_prop: the first CA block broke down");
+    if (status == 0) {
+        const int ks = kuse * s;
+        const LanczosView v = lanczos_view(c);
+        *lsteps = ks;
+        for (int j = 0; j < ks; ++j)
+            for (int i = 0; i < ks; ++i) T[i + (size_t)j * ks] = v.T[i + (size_t)j * v.ldt];
+        auto get = [&](double* dst, const double* src) -> int {
+            CAL_HIP(c, hipMemcpy2DAsync(dst, n * sizeof(double), src, v.ld * sizeof(double), n * sizeof(double), ks,
+                                        hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        if (Q_re) status = get(Q_re, v.Q);
+        if (status == 0 && Q_im) status = get(Q_im, v.Q + n);
+        if (status == 0) status = hipStreamSynchronize(c->stream) == hipSuccess ? 0 : CAL_ERR_HIP;
+    } else {
+        *lsteps = 0;
+    }
+    cal_prop_end(c);
+    return status;
+}
+
+}  // extern "C"

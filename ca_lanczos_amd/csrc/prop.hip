@@ -1,0 +1,171 @@
+// prop.hip -- the half-mixing combine of the Krylov time propagation
+// (ca_lanczos_prop.m / runLanczos.m:102-103 on stacked halves):
+//
+//   psi' = nrm * Q_c * c,   Q_c = Q(1:n,:) + i Q(n+1:2n,:),   nrm c = a + i b
+//   out[i]     = sum_j Q[i,j] a_j - Q[i+n,j] b_j
+//   out[i + n] = sum_j Q[i,j] b_j + Q[i+n,j] a_j              0 <= i < n
+//
+// One streaming pass: every Q element is read once ((2n m + 2n) * 8 bytes
+// with the store).  A lane owns kPropPairs pairs of adjacent rows and reads
+// each pair of either half with one 16-byte load; a half whose origin (or
+// whose output's origin) is not 16-byte aligned -- the lower half starts at
+// row n, n may be odd, and the columns' local origin may be shifted -- takes
+// 8-byte loads instead, and so does the single last row of an odd n.
+//
+// The summation order is fixed (the build is -ffp-contract=off, so a NumPy
+// loop reproduces the bits): accumulators start at +0.0, j ascends, and per j
+//   top = top + Qt a_j;  top = top - Qb b_j;  bot = bot + Qt b_j;  bot = bot + Qb a_j
+// one chain per output row -- the rows a lane owns give the instruction-level
+// parallelism, not split accumulators.  The coefficients are staged in LDS.
+// Every block also leaves the sum of its out^2 in partial[block] (per lane in
+// row order top then bottom, pair by pair; wave tree; the four waves in
+// order): launch_reduce turns them into the next step's squared norm without
+// another sweep, deterministically (no atomics).
+#include "cal_internal.hpp"
+
+namespace cal {
+
+namespace {
+
+typedef double pd2 __attribute__((ext_vector_type(2)));
+
+constexpr int kPropThreads = 256;
+constexpr int kPropPairs = 2;                                     // row pairs per lane
+constexpr int kPropBlockRows = 2 * kPropPairs * kPropThreads;     // rows of one half per block
+
+__device__ __forceinline__ double prop_wave_sum(double s) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, 64);
+    return s;
+}
+
+// two adjacent rows of one half: a 16-byte access when the half is aligned
+template <bool VEC>
+__device__ __forceinline__ void load2(const double* __restrict__ p, double& x0, double& x1) {
+    if (VEC) {
+        const pd2 v = *reinterpret_cast<const pd2*>(p);
+        x0 = v.x;
+        x1 = v.y;
+    } else {
+        x0 = p[0];
+        x1 = p[1];
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void store2(double* __restrict__ p, double x0, double x1) {
+    if (VEC) {
+        pd2 v;
+        v.x = x0;
+        v.y = x1;
+        *reinterpret_cast<pd2*>(p) = v;
+    } else {
+        p[0] = x0;
+        p[1] = x1;
+    }
+}
+
+template <bool VT, bool VB>
+__global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __restrict__ Q, int64_t ld, int64_t n,
+                                                               int m, const double* __restrict__ a,
+                                                               const double* __restrict__ b,
+                                                               double* __restrict__ out,
+                                                               double* __restrict__ partial) {
+    __shared__ double sa[kPropMaxCols];
+    __shared__ double sb[kPropMaxCols];
+    __shared__ double ws[kPropThreads / 64];
+    for (int j = threadIdx.x; j < m; j += kPropThreads) {
+        sa[j] = a[j];
+        sb[j] = b[j];
+    }
+    __syncthreads();
+
+    const int64_t base = (int64_t)blockIdx.x * kPropBlockRows;
+    double nrm = 0.0;
+#pragma unroll
+    for (int p = 0; p < kPropPairs; ++p) {
+        const int64_t r = base + 2 * ((int64_t)p * kPropThreads + threadIdx.x);
+        if (r + 1 < n) {
+            const double* qt = Q + r;
+            const double* qb = Q + n + r;
+            double t0 = 0.0, t1 = 0.0, b0 = 0.0, b1 = 0.0;
+#pragma unroll 4
+            for (int j = 0; j < m; ++j) {
+                double xt0, xt1, xb0, xb1;
+                load2<VT>(qt, xt0, xt1);
+                load2<VB>(qb, xb0, xb1);
+                qt += ld;
+                qb += ld;
+                const double aj = sa[j], bj = sb[j];
+                t0 = t0 + xt0 * aj;
+                t1 = t1 + xt1 * aj;
+                t0 = t0 - xb0 * bj;
+                t1 = t1 - xb1 * bj;
+                b0 = b0 + xt0 * bj;
+                b1 = b1 + xt1 * bj;
+                b0 = b0 + xb0 * aj;
+                b1 = b1 + xb1 * aj;
+            }
+            store2<VT>(out + r, t0, t1);
+            store2<VB>(out + n + r, b0, b1);
+            nrm = nrm + t0 * t0;
+            nrm = nrm + t1 * t1;
+            nrm = nrm + b0 * b0;
+            nrm = nrm + b1 * b1;
+        } else if (r < n) {  // the last row of an odd n
+            const double* qt = Q + r;
+            const double* qb = Q + n + r;
+            double t0 = 0.0, b0 = 0.0;
+            for (int j = 0; j < m; ++j) {
+                const double xt0 = *qt, xb0 = *qb;
+                qt += ld;
+                qb += ld;
+                const double aj = sa[j], bj = sb[j];
+                t0 = t0 + xt0 * aj;
+                t0 = t0 - xb0 * bj;
+                b0 = b0 + xt0 * bj;
+                b0 = b0 + xb0 * aj;
+            }
+            out[r] = t0;
+            out[n + r] = b0;
+            nrm = nrm + t0 * t0;
+            nrm = nrm + b0 * b0;
+        }
+    }
+    nrm = prop_wave_sum(nrm);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) ws[wave] = nrm;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+int prop_combine_blocks(int64_t n) {
+    const int64_t b = (n + kPropBlockRows - 1) / kPropBlockRows;
+    return (int)(b < 1 ? 1 : b);
+}
+
+hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
+                               double* out, double* partial, hipStream_t st) {
+    if (n < 1 || m < 1 || m > kPropMaxCols || ld < 2 * n) return hipErrorInvalidValue;
+    if (n > ((int64_t)1 << 40)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)prop_combine_blocks(n)), block(kPropThreads);
+    // a half takes 16-byte accesses when its rows of every column and of the
+    // output start 16-byte aligned (even leading dimension)
+    const bool even = (ld & 1) == 0;
+    const bool vt = even && aligned16(Q) && aligned16(out);
+    const bool vb = even && aligned16(Q + n) && aligned16(out + n);
+    if (vt && vb)
+        hipLaunchKernelGGL((k_prop_combine<true, true>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial);
+    else if (vt)
+        hipLaunchKernelGGL((k_prop_combine<true, false>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial);
+    else if (vb)
+        hipLaunchKernelGGL((k_prop_combine<false, true>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial);
+    else
+        hipLaunchKernelGGL((k_prop_combine<false, false>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial);
+    return hipGetLastError();
+}
+
+}  // namespace cal

@@ -902,12 +902,14 @@ int cal_create(int device, cal_ctx** out) {
 }
 
 void cal_lanczos_free_state(cal_ctx* c);  // lanczos.cpp
+void cal_prop_free_state(cal_ctx* c);     // prop.cpp
 
 void cal_destroy(cal_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     if (c->nest_stream) hipStreamSynchronize(c->nest_stream);
+    cal_prop_free_state(c);
     cal_lanczos_free_state(c);
     cal::comm_destroy(c);
     free_matrix(c);

@@ -71,6 +71,13 @@ int cal_timer_reset(cal_ctx* ctx);
 int cal_set_matrix_csc(cal_ctx* ctx, int64_t n, const int64_t* jc, const int64_t* ir, const double* pr);
 /* CSR with int64 row pointers and int32 column indices (SciPy layout). */
 int cal_set_matrix_csr(cal_ctx* ctx, int64_t n, const int64_t* rowptr, const int32_t* colind, const double* val);
+/* The 2n x 2n matrix blkdiag(H, H) of an n x n CSR H, built on the host and
+ * handed to cal_set_matrix_csr: the real form of a complex problem whose
+ * vectors are stacked, Re in rows [0, n), Im in rows [n, 2n) (the time
+ * propagator, cal_prop_*).  Each half keeps H's rows, column offsets and row
+ * patterns; the values are stored twice.  cal_matrix_info reports 2n. */
+int cal_set_matrix_csr_stacked(cal_ctx* ctx, int64_t n, const int64_t* rowptr, const int32_t* colind,
+                               const double* val);
 /* Row-slab of a distributed matrix: rows [row0, row0+nlocal) of the global
  * n_global x n_global matrix, global column indices.  Requires a communicator
  * (cal_comm_*) when nranks > 1. */
@@ -276,6 +283,69 @@ int cal_restarted_ca_lanczos(cal_ctx* ctx, const double* r, int max_lanczos, int
 int cal_impl_restarted_ca_lanczos(cal_ctx* ctx, const double* r, int max_lanczos, int n_wanted, int s,
                                   const char* basis, const char* orth, double tol, double* conv_eigs,
                                   double* Q_conv, double* ritz_est, cal_restart_info* info);
+
+/* ---- Krylov time propagation psi(t+dt) = exp(-i*dt*H) psi(t) -------------- */
+/* ca_lanczos_prop.m:3-135 driven as runLanczos.m:84-131 drives it, for a real
+ * symmetric H and a complex psi = u + i v.  Hermitian Lanczos on psi has real
+ * recurrence coefficients, so it is real CA-Lanczos on blkdiag(H, H)
+ * (cal_set_matrix_csr_stacked) started from the stacked vector [u; v]: same
+ * T, complex basis Q(1:n,:) + i Q(n+1:2n,:).  One rank only
+ * (CAL_ERR_UNSUPPORTED with a communicator of more ranks). */
+typedef struct cal_prop_info {
+    int steps;            /* time steps taken                                    */
+    int lsteps;           /* Lanczos vectors (k*s) of the last step              */
+    int lsteps_max;       /* largest and ...                                     */
+    long long lsteps_sum; /* ... summed lsteps over all steps                    */
+    double residual;      /* |dt*b(k)*c(k*s)*nrm| of the last step (:123)        */
+    double residual_max;  /* its maximum over all steps                          */
+    double norm;          /* 2-norm of the current state                         */
+    int nshifts;          /* Newton shifts in use (Leja order), 0: monomial      */
+    double shifts[64];
+    int breakdowns;       /* blocks dropped: breakdown or a non-finite residual  */
+    int rank_deficient;   /* blocks normalize flagged 'Rank deficient' (kept, as
+                             the reference keeps them: normalize.m:21-27)        */
+    double ms;            /* wall time inside cal_prop_step                      */
+} cal_prop_info;
+
+/* out = nrm * Q_c * c on stacked halves (the propagator's combine kernel on
+ * host data): Q is 2n x m (ld 2n), c = c_re + i c_im (m entries, m <= 512),
+ *   out_re = Q(1:n,:) c_re - Q(n+1:2n,:) c_im,
+ *   out_im = Q(1:n,:) c_im + Q(n+1:2n,:) c_re,
+ * each output row one chain over ascending j, *norm2 (may be
+ * NULL) = sum of out_re^2 + out_im^2.  Needs no matrix on the context. */
+int cal_prop_combine(cal_ctx* ctx, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
+                     double* out_re, double* out_im, double* norm2);
+
+/* Step-wise propagator.  The context's matrix must have 2n rows (blkdiag(H,
+ * H)).  psi_im may be NULL (real start).  1 <= s <= 31, s*max_blocks <= 512;
+ * basis "monomial" or "newton".  With eigest (neig >= s values) the Newton
+ * shifts are leja(real(eigest)) (:38-41); with none, the first step runs
+ * lanczos(A,psi,2s,'local') (:33) and every later step reuses its shifts
+ * (runLanczos.m:93-96).  The state, Q and the norm stay on the device. */
+int cal_prop_begin(cal_ctx* ctx, int64_t n, const double* psi_re, const double* psi_im, int s, int max_blocks,
+                   const char* basis, const double* eigest, int neig);
+/* nsteps time steps of size dt.  Each: normalise, CA blocks with orth 'local'
+ * (the library's second-pass rule where :78 passes doreorth = false), after
+ * block k the residual |dt*b(k)*c(k*s)*nrm| with c = expm(-i*dt*T(1:ks,1:ks))
+ * e_1 (:122-123); with adaptive != 0 the step stops at the first k with
+ * residual < tol and k*s >= 3 (:124); psi <- nrm*Q_c*c.  A block that breaks
+ * down (rho_t == 0, a non-finite T or residual) is dropped with those after
+ * it and counted in the info; if it is the first block the call returns
+ * CAL_WARN_BREAKDOWN and the state is unchanged.  A block that normalize
+ * flags 'Rank deficient' is counted and kept, as the reference keeps it. */
+int cal_prop_step(cal_ctx* ctx, double dt, double tol, int adaptive, int nsteps);
+/* The state (either pointer may be NULL) and the counters; the only
+ * device-to-host copy of the state. */
+int cal_prop_get(cal_ctx* ctx, double* psi_re, double* psi_im, cal_prop_info* info);
+int cal_prop_end(cal_ctx* ctx);
+
+/* [T,Q,lsteps] = ca_lanczos_prop(A,r0,s,m,dt,tol,basis,eigest,adaptive)
+ * (ca_lanczos_prop.m:3-135) with r0 = r_re + i r_im (r_im may be NULL) on the
+ * stacked matrix: T is *lsteps x *lsteps (ld *lsteps; room for s*m squared),
+ * Q_re / Q_im n x *lsteps (room for n x s*m; either may be NULL). */
+int cal_ca_lanczos_prop(cal_ctx* ctx, int64_t n, const double* r_re, const double* r_im, int s, int m, double dt,
+                        double tol, const char* basis, const double* eigest, int neig, int adaptive, double* T,
+                        double* Q_re, double* Q_im, int* lsteps);
 
 /* ---- multi-GPU (row slabs, RCCL over xGMI) ------------------------------ */
 /* 128-byte RCCL unique id; broadcast it out of band (e.g. torch.distributed). */

@@ -45,6 +45,15 @@ int cal_tridiag_eigvals(int n, const double* alpha, const double* beta, double* 
  * column signs).  H (ldh >= m) and W (ldw >= m) column-major, in place. */
 int cal_qrstep(int m, double* H, int ldh, double* W, int ldw, double mu);
 
+/* c = expm(-i*dt*T) * e_1 for a general real m x m T (ldt >= m), 1 <= m <=
+ * 512: the coefficients of the Krylov time propagation
+ * (ca_lanczos_prop.m:122, runLanczos.m:102-103).  T is exponentiated as it
+ * is (the CA loop's T is only nearly symmetric; it is not symmetrised):
+ * scaling and squaring with a Taylor series in complex arithmetic, no LAPACK.
+ * CAL_ERR_ARG outside 1 <= m <= 512 or for a non-finite dt, CAL_ERR_NUMERIC
+ * for a non-finite T. */
+int cal_expm_col1(int m, const double* T, int ldt, double dt, double* c_re, double* c_im);
+
 /* Residency generation of the MEX shims' device copies of A (mex/
  * cal_mex_common.h).  Every shim keeps A resident across calls and re-uploads
  * it when the pointers, nnz, a sampled digest of jc/ir/pr or this

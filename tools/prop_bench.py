@@ -1,0 +1,170 @@
+#!/usr/bin/env python
+"""Time steps/s of the Krylov time propagator on a stacked Laplacian.
+
+  python tools/prop_bench.py [--workload lap3d_215] [--s 8] [--blocks 3]
+                             [--steps 50] [--warmup 5] [--out profiles/prop/NAME.json]
+
+Workload: psi <- exp(-i dt H) psi with H = lap3d_N (or lap2d_N), embedded as
+blkdiag(H, H) (2n rows), Newton basis, a complex Gaussian packet as the start
+state.  Measured, in runs of their own:
+  1. wall time of --steps time steps after --warmup (timers off): steps/s;
+  2. the same steps with the library's HIP-event timers on: per-kind kernel
+     time per time step;
+  3. the steady-state outer iteration of a plain CA-Lanczos loop on the same
+     stacked matrix (3 warm-up iterations, 12 timed), the yardstick "blocks x
+     the per-outer-iteration time at twice the rows";
+  4. the combine kernel alone through cal_prop_combine (the library timer
+     brackets the kernel only): mean time and rate over (2n m + 2n) 8 bytes;
+  5. cal_expm_col1 on T's of s, 2s, ... s*blocks rows on the host.
+Also records what cal_spmv_plane_info / cal_spmv_format report for the
+stacked matrix and for H alone, whether the stacked SpMV equals H applied to
+each half bit for bit, and the norm drift over the run (unitarity).
+Prints one JSON line; --out also writes it to a file.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="lap3d_215")
+    ap.add_argument("--s", type=int, default=8)
+    ap.add_argument("--blocks", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--timed-steps", type=int, default=10, help="time steps of the run with the timers on")
+    ap.add_argument("--dt", type=float, default=0.05)
+    ap.add_argument("--start", default="packet", choices=("packet", "random"),
+                    help="start state: a smooth complex Gaussian packet, or random (a well-conditioned Krylov basis)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    import ca_lanczos_amd as cal
+    kind, N = a.workload.split("_")
+    N = int(N)
+    dim = 3 if kind == "lap3d" else 2
+    H = cal.matrices.laplacian_3d(N) if dim == 3 else cal.matrices.laplacian_2d(N)
+    n = H.shape[0]
+    idx = np.arange(n)
+    coords = [(idx // N ** d) % N for d in range(dim)]
+    r2 = sum((c - 0.5 * (N - 1)) ** 2 for c in coords)
+    phase = sum(k * c for k, c in zip((0.7, 0.3, 0.2), coords))
+    psi0 = np.exp(-r2 / (2 * (N / 8.0) ** 2)) * np.exp(1j * phase)
+    del idx, coords, r2, phase
+    if a.start == "random":
+        rng = np.random.RandomState(1)
+        psi0 = rng.randn(n) + 1j * rng.randn(n)
+
+    res = dict(workload=a.workload, start=a.start, n=n, rows=2 * n, s=a.s, blocks=a.blocks, m=a.s * a.blocks, dt=a.dt,
+               steps=a.steps, warmup=a.warmup)
+    alone = cal.Context().set_matrix(H)
+    res["H_alone"] = dict(spmv_format=alone.spmv_format(), plane_info=alone.spmv_plane_info())
+    half_re, half_im = alone.spmv(psi0.real), alone.spmv(psi0.imag)
+    alone.close()
+
+    ctx = cal.Context()
+    P = cal.Propagator(H, psi0, a.s, a.blocks, basis="newton", ctx=ctx)
+    res["stacked"] = dict(spmv_format=ctx.spmv_format(), plane_info=ctx.spmv_plane_info(),
+                          pair_info=ctx.spmv_pair_info(), matrix_info=ctx.matrix_info())
+    # the stacked SpMV is H on each half, bit for bit (also across the seam at row n)
+    y = ctx.spmv(np.concatenate([psi0.real, psi0.imag]))
+    res["spmv_stacked_equals_halves"] = bool(np.array_equal(y[:n], half_re) and np.array_equal(y[n:], half_im))
+    del y, half_re, half_im
+    n0 = P.info()["norm"]
+    P.step(a.dt, a.warmup)
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    P.step(a.dt, a.steps)
+    ctx.synchronize()
+    wall = time.perf_counter() - t0
+    info = P.info()
+    res.update(steps_per_s=a.steps / wall, ms_per_step=1e3 * wall / a.steps, norm_drift=abs(info["norm"] - n0),
+               lsteps=info["lsteps"], breakdowns=info["breakdowns"], rank_deficient=info["rank_deficient"],
+               residual_max=info["residual_max"], tsqr_fold_stats=ctx.tsqr_fold_stats(),
+               normalize=ctx.normalize_backend())
+
+    # 2. the kernel classes of a time step
+    ctx.timer_enable(True)
+    ctx.timer_reset()
+    P.step(a.dt, a.timed_steps)
+    ctx.synchronize()
+    prop_t = {k: ctx.timer_read(k) for k in ("spmv", "gram", "apply", "other")}
+    prop_b = ctx.timer_bytes("apply")
+    ctx.timer_enable(False)
+    res["kernel_ms_per_step"] = {k: v[1] / a.timed_steps for k, v in prop_t.items()}
+    P.close()
+
+    # 3. the steady-state outer iteration of the plain CA-Lanczos loop on the
+    # same matrix (bench.py's measure: warm-up iterations, then timed ones)
+    x0 = np.concatenate([psi0.real, psi0.imag])
+    wu, it = 3, 12
+    ctx.lanczos_begin(x0, a.s, wu + it, "newton", "local")
+    for _ in range(wu):
+        ctx.lanczos_step(False)
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(it):
+        ctx.lanczos_step(False)
+    ctx.synchronize()
+    res["outer_iteration_ms"] = 1e3 * (time.perf_counter() - t0) / it
+    ctx.lanczos_end()
+
+    # the combine kernel alone, through the host-pointer entry (its timer
+    # brackets the kernel only): one untimed launch, then three timed ones
+    Q = np.ones((2 * n, a.s * a.blocks), order="F")
+    c = np.exp(1j * np.arange(a.s * a.blocks)) / np.sqrt(a.s * a.blocks)
+    ctx.prop_combine(Q, c)
+    ctx.timer_enable(True)
+    ctx.timer_reset()
+    for _ in range(3):
+        ctx.prop_combine(Q, c)
+    cnt, cms = ctx.timer_read("apply")
+    cbytes = ctx.timer_bytes("apply")
+    ctx.timer_enable(False)
+    del Q
+    comb_ms = cms / cnt
+    res["combine"] = dict(launches=cnt, ms=comb_ms, bytes=cbytes / cnt,
+                          expected_bytes=(2.0 * n * a.s * a.blocks + 2.0 * n) * 8,
+                          tb_per_s=cbytes / (cms * 1e-3) / 1e12)
+    ctx.close()
+
+    # 4. the host exponential of one time step (after every block)
+    rng = np.random.RandomState(0)
+    tex = 0.0
+    for k in range(1, a.blocks + 1):
+        m = k * a.s
+        T = np.diag(3 + rng.rand(m)) + np.diag(rng.rand(m - 1), 1)
+        T = T + np.triu(T, 1).T
+        t0 = time.perf_counter()
+        for _ in range(20):
+            cal.expm_col1(T, a.dt)
+        tex += (time.perf_counter() - t0) / 20
+    res["expm_ms_per_step"] = 1e3 * tex
+    ms = res["ms_per_step"]
+    loop = a.blocks * res["outer_iteration_ms"]
+    # blocks x the steady outer iteration, the combine, the host exponential;
+    # the rest is the begin (normalise, T reset) and what the first block
+    # (normalize of s + 1 columns) costs beyond a steady one
+    res["share"] = dict(blocks_x_outer_iteration=loop / ms, combine=comb_ms / ms,
+                        expm=res["expm_ms_per_step"] / ms,
+                        begin_first_block_and_rest=1.0 - (loop + comb_ms + res["expm_ms_per_step"]) / ms)
+    line = json.dumps(res, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o))
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
