@@ -3,13 +3,14 @@
 Drop-in for the reference's hot-path functions (SpMV.m,
 matrix_powers_{monomial,newton}.m, tsqr.m, cholqr.m, project.m,
 normalize.m, projectAndNormalize.m, ca_lanczos.m, restarted_ca_lanczos.m,
-impl_restarted_ca_lanczos.m, ca_lanczos_prop.m) behind the C ABI of
+impl_restarted_ca_lanczos.m, ca_lanczos_prop.m, lanczos.m) behind the C ABI of
 include/calanczos.h; see DESIGN.md and INTEGRATION.md.
 """
 from ._lib import CalError, LIB_PATH  # noqa: F401  (raises ImportError if the .so is missing)
 from .api import (  # noqa: F401
     CALanczosOutput,
     Context,
+    LanczosOutput,
     Propagator,
     SpMV,
     ca_lanczos,
@@ -21,6 +22,8 @@ from .api import (  # noqa: F401
     default_context,
     eig,
     expm_col1,
+    lanczos,
+    lanczos_ex,
     leja,
     matlab_rand,
     matrix_powers_monomial,

@@ -68,6 +68,13 @@ class PropInfo(ctypes.Structure):
     ]
 
 
+class StdLanczosInfo(ctypes.Structure):
+    _fields_ = [
+        ("steps", c_int), ("breakdown", c_int), ("fused", c_int), ("n_orth_breaks", c_int), ("n_ritz_locked", c_int),
+        ("norm_A", c_double), ("loop_ms", c_double), ("diag_ms", c_double),
+    ]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, dp, c_int64)
 EXCHANGE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, dp, c_int64, dp, c_int64)
 
@@ -140,6 +147,14 @@ SIGNATURES = [
     ("cal_prop_end", c_int, [c_void_p]),
     ("cal_ca_lanczos_prop", c_int,
      [c_void_p, c_int64, dp, dp, c_int, c_int, c_double, c_double, c_char_p, dp, c_int, c_int, dp, dp, dp, ip]),
+    ("cal_lanczos", c_int, [c_void_p, dp, c_int, c_char_p, c_int, dp, dp, dp, dp, POINTER(StdLanczosInfo)]),
+    ("cal_std_lanczos_begin", c_int, [c_void_p, dp, c_int, c_char_p, c_int]),
+    ("cal_std_lanczos_step", c_int, [c_void_p, c_int, c_int]),
+    ("cal_std_lanczos_get", c_int, [c_void_p, dp, dp, dp, dp, POINTER(StdLanczosInfo)]),
+    ("cal_std_lanczos_get_Q", c_int, [c_void_p, c_int64, c_int, dp]),
+    ("cal_std_lanczos_end", c_int, [c_void_p]),
+    ("cal_spmv_lanczos", c_int, [c_void_p, dp, dp, c_double, dp, dp]),
+    ("cal_spmv_lanczos_fused", c_int, [c_void_p, ip]),
     ("cal_comm_unique_id", c_int, [c_void_p]),
     ("cal_comm_init_rccl", c_int, [c_void_p, c_int, c_int, c_void_p]),
     ("cal_comm_init_host", c_int, [c_void_p, c_int, c_int, ALLREDUCE_FN, EXCHANGE_FN, c_void_p]),

@@ -319,6 +319,65 @@ class Context:
     def lanczos_end(self):
         check(self.h, lib.cal_lanczos_end(self.h))
 
+    # -- step-wise standard Lanczos (lanczos.m) -----------------------------------
+    def std_lanczos_begin(self, r, maxiter, orth="local", keep_Q=True):
+        r = f64(r).ravel()
+        check(self.h, lib.cal_std_lanczos_begin(self.h, ptr(r), int(maxiter), _std_orth(orth).encode(),
+                                                1 if keep_Q else 0), "std_lanczos_begin")
+        self._slz = int(maxiter)
+
+    def std_lanczos_step(self, nsteps=1, diagnostics=False):
+        """Enqueue nsteps more steps; returns the status (CAL_WARN_BREAKDOWN = 2 once a beta_j broke down)."""
+        return check(self.h, lib.cal_std_lanczos_step(self.h, int(nsteps), 1 if diagnostics else 0), "std_lanczos_step")
+
+    def std_lanczos_get(self):
+        """(alpha, beta, ritz_rnorm, orth_err, info dict) of the steps kept so far."""
+        m = self._slz
+        al, be, oe = np.zeros(m), np.zeros(m), np.zeros(m)
+        rn = np.zeros((m, m), order="F")
+        info = _lib.StdLanczosInfo()
+        st = check(self.h, lib.cal_std_lanczos_get(self.h, ptr(al), ptr(be), ptr(rn), ptr(oe), ctypes.byref(info)),
+                   "std_lanczos_get")
+        k = info.steps
+        return al[:k].copy(), be[:k].copy(), np.array(rn[:k, :k]), oe[:k].copy(), _std_info(info, st)
+
+    def std_lanczos_get_Q(self, col0, ncols):
+        Q = np.zeros((self.n, ncols), order="F")
+        check(self.h, lib.cal_std_lanczos_get_Q(self.h, col0, ncols, ptr(Q)), "std_lanczos_get_Q")
+        return Q
+
+    def std_lanczos_end(self):
+        check(self.h, lib.cal_std_lanczos_end(self.h))
+
+    def spmv_lanczos(self, x, xprev=None, beta2=0.0):
+        """The fused Lanczos SpMV on host data: (y, dot) with y = A x - sqrt(beta2) xprev, dot = y'x."""
+        x = f64(x).ravel()
+        xp = None if xprev is None else f64(xprev).ravel()
+        y = np.zeros(self.n)
+        dot = np.zeros(1)
+        check(self.h, lib.cal_spmv_lanczos(self.h, ptr(x), ptr(xp), float(beta2), ptr(y), ptr(dot)), "spmv_lanczos")
+        return y, float(dot[0])
+
+    def spmv_lanczos_fused(self):
+        """Whether the context's matrix takes the fused Lanczos SpMV mode."""
+        f = ctypes.c_int()
+        check(self.h, lib.cal_spmv_lanczos_fused(self.h, ctypes.byref(f)), "spmv_lanczos_fused")
+        return bool(f.value)
+
+
+def _std_orth(orth):
+    """lanczos.m:20-32: the option check (a numeric orth is num2str'ed there)."""
+    o = orth.lower() if isinstance(orth, str) else str(orth)
+    if o not in ("local", "full", "selective", "periodic"):
+        raise ValueError("lanczos.m: Invalid option value for orth: %s" % orth)
+    return o
+
+
+def _std_info(info, status):
+    return dict(steps=info.steps, breakdown=info.breakdown, fused=info.fused, n_orth_breaks=info.n_orth_breaks,
+                n_ritz_locked=info.n_ritz_locked, norm_A=info.norm_A, loop_ms=info.loop_ms, diag_ms=info.diag_ms,
+                status=status)
+
 
 # ---------------------------------------------------------------------------
 # context cache: one resident copy per matrix object (MATLAB passes A by value
@@ -613,6 +672,44 @@ def ca_lanczos_ex(A, r, s, iter, basis, orth="local", diagnostics=True, return_Q
 def ca_lanczos(A, r, s, iter, basis, orth="local"):
     """``[T,Q,ritz_rnorm,orth_err] = ca_lanczos(A,r,s,iter,basis,orth)`` -- ca_lanczos.m:24-86."""
     out = ca_lanczos_ex(A, r, s, iter, basis, orth, diagnostics=True, return_Q=True)
+    return out.T, out.Q, out.ritz_rnorm, out.orth_err
+
+
+# ---------------------------------------------------------------------------
+# standard Lanczos (lanczos.m), the other half of the reference's comparisons
+# ---------------------------------------------------------------------------
+@dataclass
+class LanczosOutput:
+    T: np.ndarray
+    Q: np.ndarray | None
+    alpha: np.ndarray
+    beta: np.ndarray
+    ritz_rnorm: np.ndarray
+    orth_err: np.ndarray
+    info: dict = field(default_factory=dict)
+
+
+def lanczos_ex(A, r, maxiter, orth="local", diagnostics=False, return_Q=True, ctx=None):
+    """lanczos.m:18-60 with alpha, beta and the counters.  return_Q = False
+    with orth 'local' and no diagnostics keeps three columns on the device."""
+    o = _std_orth(orth)
+    ctx = ctx or context_for(A)
+    keep = bool(return_Q or diagnostics or o != "local")
+    ctx.std_lanczos_begin(r, maxiter, o, keep_Q=keep)
+    try:
+        ctx.std_lanczos_step(int(maxiter), diagnostics)
+        al, be, rn, oe, info = ctx.std_lanczos_get()
+        k = info["steps"]
+        Q = ctx.std_lanczos_get_Q(0, k) if return_Q else None
+    finally:
+        ctx.std_lanczos_end()
+    T = np.diag(al) + np.diag(be[: max(k - 1, 0)], 1) + np.diag(be[: max(k - 1, 0)], -1)  # lanczos.m:131
+    return LanczosOutput(T=T, Q=Q, alpha=al, beta=be, ritz_rnorm=rn, orth_err=oe, info=info)
+
+
+def lanczos(A, r, maxiter, orth="local"):
+    """``[T,Q,ritz_rnorm,orth_err] = lanczos(A,r,maxiter,orth)`` -- lanczos.m:18-60."""
+    out = lanczos_ex(A, r, maxiter, orth, diagnostics=True, return_Q=True)
     return out.T, out.Q, out.ritz_rnorm, out.orth_err
 
 

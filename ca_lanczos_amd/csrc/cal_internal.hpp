@@ -89,6 +89,10 @@ struct SpmvArgs {
     const double* xnrm = nullptr;
     int xcd;              // XCD-contiguous block order (set by launch_spmv)
     int nt = 0;           // col / val loaded non-temporally (matrix larger than the Infinity Cache)
+    // mode 4 (the fused Lanczos step): y = A x - sqrt(*pb2) xprev (xprev / pb2
+    // null: y = A x) and dotp[block] = the block's sum of y .* x
+    const double* pb2 = nullptr;
+    double* dotp = nullptr;
 };
 
 // Row-pattern storage ("PSR"): row r is pattern pat[r], a sequence of
@@ -141,6 +145,9 @@ struct PatArgs {
     // stored pair t + gap, i.e. rows [0, 2 gap_at) and [2 (gap_at + gap),
     // 2 gap + n) relative to the origin; n counts the rows of both ranges
     int64_t gap_at = 0, gap = 0;
+    // mode 4, as SpmvArgs (plane march and pair kernel; one range)
+    const double* pb2 = nullptr;
+    double* dotp = nullptr;
 };
 constexpr int kPairSplit = 0xFFFF;
 // the plane march: rows of a plane per block (4 waves x 64 lanes x 2 rows)
@@ -215,10 +222,15 @@ struct DevMatrix {
 struct Comm;  // comm.cpp
 struct LanczosState;  // lanczos.cpp
 struct PropState;     // prop.cpp
+struct StdLanczosState;  // lanczos_std.cpp
 
 // Launchers (kernels.hip).  All enqueue on `st` and return hipError_t.
 hipError_t launch_spmv(const SpmvArgs& a, hipStream_t st);
 hipError_t launch_spmv_pat(const PatArgs& a, hipStream_t st);
+// mode 4's grid = its number of y'x partials (0: this storage has no fused
+// Lanczos mode -- the row-pattern kernels k_spmv_pat / k_spmv_pat_lds)
+int spmv_lanczos_blocks(const SpmvArgs& a);
+int spmv_pat_lanczos_blocks(const PatArgs& a);
 // C (wa x wb, column-major ldc = 16*ceil(wa/16)) partials; see kernels.hip.
 struct GramPlan {
     int nta;    // A tiles of 16 columns
@@ -325,6 +337,11 @@ hipError_t launch_normest_norms_only(const double* x, const double* y, int64_t n
                                      hipStream_t st);
 hipError_t launch_pro_step(double* r, const double* qprev, const double* pb_prev, const double* q, double* qnext,
                            int64_t n, double* part, double* d_alpha, double* d_beta2, hipStream_t st);
+// the tail of a fused Lanczos step (kernels.hip): alpha = sum of the np
+// partials pa -> *d_alpha, r -= alpha q, beta^2 = r'r -> *d_beta2 (pb:
+// dot_blocks(n) doubles of scratch), qnext = r / beta
+hipError_t launch_pro_tail(double* r, const double* q, double* qnext, int64_t n, const double* pa, int np, double* pb,
+                           double* d_alpha, double* d_beta2, hipStream_t st);
 hipError_t launch_axpy_sub_dev(double* y, const double* x, const double* pa, bool take_sqrt, int64_t n,
                                hipStream_t st);
 hipError_t launch_div_sqrt(double* y, const double* x, const double* nn, int64_t n, hipStream_t st);  // y = x / sqrt(*nn)
@@ -505,6 +522,7 @@ struct cal_ctx {
 
     cal::LanczosState* lz = nullptr;
     cal::PropState* prop = nullptr;  // the time propagator's state (prop.cpp)
+    cal::StdLanczosState* slz = nullptr;  // standard Lanczos (lanczos_std.cpp)
     cal::Comm* comm = nullptr;
 
     bool timing = false;
@@ -699,6 +717,13 @@ struct LanczosView {
 };
 LanczosView lanczos_view(cal_ctx* c);
 
+// normest(A) on the device, synchronous (lanczos.cpp normest_dev; uses work columns 0, 1)
+int normest_run(cal_ctx* c, double* out);
+// compute_ritz_rnorm for device Q (k columns at Qd, leading dimension A.ld,
+// local origin): cal_compute_ritz_rnorm after its upload (lanczos.cpp; uses
+// work columns [k, 2k))
+int ritz_rnorm_dev(cal_ctx* c, const double* Qd, int k, const double* Vp, const double* d, double* rn);
+
 // Device block operations (blockorth.cpp).  All matrices column-major; n is
 // the number of (local) rows of the panels.
 // Gram: out (wa x wb, ld wa) = A^T B (allreduced across ranks), on host.
@@ -742,6 +767,11 @@ int halo_exchange(cal_ctx* c, double* x);
 // y = A (x / sqrt(*xnrm)), xnrm a device scalar.
 int spmv_dev(cal_ctx* c, const double* x, double* y, int mode, double shift, double im2,
              const double* xprev, const double* xnrm = nullptr);
+// The fused Lanczos step (SpMV mode 4, one rank): y = A x - sqrt(*pb2) xprev
+// (xprev / pb2 null: y = A x) and dotp[i] = block i's sum of y .* x, i <
+// spmv_lanczos_parts (0: the matrix's SpMV kernel has no fused mode).
+int spmv_lanczos_parts(const cal_ctx* c, const double* x, const double* xprev, double* y);
+int spmv_lanczos_dev(cal_ctx* c, const double* x, const double* xprev, const double* pb2, double* y, double* dotp);
 // y = A x (mode 0, or 3 on CSR) on stream st without timers or statistics
 // (one rank; the asynchronous normest)
 hipError_t spmv_on_stream(const cal_ctx* c, const double* x, double* y, int mode, const double* xnrm, hipStream_t st);

@@ -9,6 +9,9 @@
 //   k_spmv          CSR-stream SpMV: coalesced val/col loads of a row block,
 //                   products staged in LDS, sequential per-row sums
 //                   (bit-exact), fused Newton shift (matrix_powers_newton.m:31-47).
+//                   MODE 4 (here, in k_spmv_pair and in k_spmv_planes): the
+//                   standard Lanczos step y = A x - beta xprev with the block
+//                   partials of y'x (lanczos.m:103-107; lz_sub, lz_block_sum).
 //   k_spmv_pat_lds, k_spmv_pair
 //                   row-pattern SpMV (lossless pattern table, one / two rows
 //                   per lane), same arithmetic, same shift epilogue; the pair
@@ -107,6 +110,31 @@ __device__ __forceinline__ T ldnt(const T* p) {
     else return *p;
 }
 
+// MODE 4, the fused Lanczos step (lanczos.m:103-107): y = A x - b xprev with
+// b = sqrt(*pb2) still on the device, and the block's partial of y'x.  The
+// product b * xprev and the subtraction round separately (k_pro_dot's
+// arithmetic); without xprev the subtrahend is +0.0, which leaves the row sum
+// (never -0.0) unchanged: the bits of MODE 0.  q is loaded from x then, so no
+// load sits behind a branch.
+__device__ __forceinline__ double wave_sum(double v);
+__device__ __forceinline__ double lz_sub(double sum, double b, double q, bool has) {
+    double t = b * q;
+    t = has ? t : 0.0;
+    return sum - t;
+}
+// fixed-order block sum over NW waves (ws: NW doubles of LDS nobody reads any more)
+template <int NW>
+__device__ __forceinline__ double lz_block_sum(double s, double* ws) {
+    s = wave_sum(s);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) ws[wave] = s;
+    __syncthreads();
+    double t = ws[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) t = t + ws[w];
+    return t;
+}
+
 template <int MODE, int NIT, bool NT, int V>
 __global__ __launch_bounds__(kSpmvThreads) void k_spmv(SpmvArgs a) {
     __shared__ double prod[kSpmvNnz];
@@ -118,6 +146,10 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv(SpmvArgs a) {
     // MODE 3: normest's S * (x / norm(x)), the division per gathered element
     // (MATLAB's x = x/normx, then S*x: the same quotients and products)
     const double sx = MODE == 3 ? sqrt(*a.xnrm) : 1.0;
+    const bool lzhas = MODE == 4 && a.xprev && a.pb2;
+    const double lzb = lzhas ? sqrt(*a.pb2) : 0.0;
+    const double* lzq = lzhas ? a.xprev : a.x;
+    double lzd = 0.0;  // MODE 4: the thread's y * x
     if (cnt <= kSpmvNnz) {
         if (cnt > 0) {
             // all loads first (clamped, never branched around: one vmcnt wait
@@ -156,7 +188,13 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv(SpmvArgs a) {
             const int q0 = a.rowptr[r] - p0, q1 = a.rowptr[r + 1] - p0;
             double sum = 0.0;
             for (int j = q0; j < q1; ++j) sum = sum + prod[j];
-            a.y[r] = spmv_epilogue<MODE>(sum, a, r);
+            if (MODE == 4) {
+                const double y = lz_sub(sum, lzb, lzq[r], lzhas);
+                a.y[r] = y;
+                lzd = y * a.x[r];
+            } else {
+                a.y[r] = spmv_epilogue<MODE>(sum, a, r);
+            }
         }
     } else {
         // one long row (> kSpmvNnz nonzeros): chunked, still summed in order
@@ -173,7 +211,20 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv(SpmvArgs a) {
                 for (int j = 0; j < m; ++j) sum = sum + prod[j];
             __syncthreads();
         }
-        if (tid == 0) a.y[r0] = spmv_epilogue<MODE>(sum, a, r0);
+        if (MODE == 4) {
+            if (tid == 0) {  // the one thread that holds the row's sum
+                const double y = lz_sub(sum, lzb, lzq[r0], lzhas);
+                a.y[r0] = y;
+                lzd = y * a.x[r0];
+            }
+        } else if (tid == 0) {
+            a.y[r0] = spmv_epilogue<MODE>(sum, a, r0);
+        }
+    }
+    if constexpr (MODE == 4) {
+        __shared__ double ws[kSpmvThreads / 64];
+        const double s = lz_block_sum<kSpmvThreads / 64>(lzd, ws);
+        if (tid == 0) a.dotp[b] = s;
     }
 }
 
@@ -205,6 +256,8 @@ static hipError_t launch_spmv_mode(const SpmvArgs& a, int nit, hipStream_t st) {
     return a.nt ? launch_spmv_mode2<MODE, true, 1>(a, nit, st) : launch_spmv_mode2<MODE, false, 1>(a, nit, st);
 }
 
+int spmv_lanczos_blocks(const SpmvArgs& a) { return a.nblk; }
+
 hipError_t launch_spmv(const SpmvArgs& a0, hipStream_t st) {
     if (a0.nblk <= 0) return hipSuccess;
     SpmvArgs a = a0;
@@ -216,6 +269,7 @@ hipError_t launch_spmv(const SpmvArgs& a0, hipStream_t st) {
         case 1: return launch_spmv_mode<1>(a, nit, st);
         case 2: return launch_spmv_mode<2>(a, nit, st);
         case 3: return a.xnrm ? launch_spmv_mode<3>(a, nit, st) : hipErrorInvalidValue;
+        case 4: return a.dotp ? launch_spmv_mode<4>(a, nit, st) : hipErrorInvalidValue;
         default: return hipErrorInvalidValue;
     }
 }
@@ -232,7 +286,7 @@ hipError_t launch_spmv(const SpmvArgs& a0, hipStream_t st) {
 // (xcd_remap: defined above k_spmv)
 
 // fixed-order butterfly sum over the 64 lanes of a wave
-__device__ __forceinline__ double wave_sum(double v) {
+__device__ __forceinline__ double wave_sum(double v) {  // (declared above k_spmv)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
     return v;
@@ -430,6 +484,8 @@ __global__ __launch_bounds__(TB) void k_spmv_pair(PatArgs a, const uint16_t* __r
     // loads depend on neither the id nor the table and leave first
     double2 xc[CANON ? MAXLEN : 1];
     double2 xs = make_double2(0.0, 0.0), xp = make_double2(0.0, 0.0);  // shift terms
+    const bool lzhas = MODE == 4 && a.xprev && a.pb2;  // MODE 4: see lz_sub
+    const double lzb = lzhas ? sqrt(*a.pb2) : 0.0;
     {
         const int64_t r0 = 2 * t;
         bool mid = false;
@@ -445,6 +501,7 @@ __global__ __launch_bounds__(TB) void k_spmv_pair(PatArgs a, const uint16_t* __r
             else xs = ld16(a.x + rc);
         }
         if (MODE == 2) xp = ld16(a.xprev + rc);
+        if (MODE == 4) xp = ld16((lzhas ? a.xprev : a.x) + rc);
     }
     for (int i = tid; i < a.npent; i += TB) {
         s_pv[i] = ppval[i];
@@ -453,7 +510,9 @@ __global__ __launch_bounds__(TB) void k_spmv_pair(PatArgs a, const uint16_t* __r
     if (!CANON)
         for (int i = tid; i < a.nppat; i += TB) s_pinfo[i] = ppinfo[i];
     __syncthreads();
-    if (tc >= npairs) return;
+    // the thread's rows; returns its y .* x (MODE 4, else unused)
+    auto rows = [&]() -> double {
+    if (tc >= npairs) return 0.0;
     const int64_t r = 2 * t;
     if (id != kPairSplit) {  // both rows exist (the lone last row is split)
         // canonical tables: every pair pattern has MAXLEN entries in one
@@ -482,7 +541,10 @@ __global__ __launch_bounds__(TB) void k_spmv_pair(PatArgs a, const uint16_t* __r
             y0 = ((CANON || e < pi.y) && (code[e] & 1)) ? a0 : y0;
             y1 = ((CANON || e < pi.y) && (code[e] & 2)) ? a1 : y1;
         }
-        if (MODE != 0) {
+        if (MODE == 4) {
+            y0 = lz_sub(y0, lzb, xp.x, lzhas);
+            y1 = lz_sub(y1, lzb, xp.y, lzhas);
+        } else if (MODE != 0) {
             const double u0 = a.shift * xs.x, u1 = a.shift * xs.y;
             y0 = y0 - u0;
             y1 = y1 - u1;
@@ -496,9 +558,10 @@ __global__ __launch_bounds__(TB) void k_spmv_pair(PatArgs a, const uint16_t* __r
         o.x = y0;
         o.y = y1;
         *reinterpret_cast<double2*>(a.y + r) = o;
-        return;
+        return y0 * xs.x + y1 * xs.y;
     }
     // split pair: each row on its own from the row tables
+    double d = 0.0;
     for (int k = 0; k < 2 && r + k < a.n + 2 * a.gap; ++k) {
         const int64_t rr = r + k;
         const int2 pi = a.pinfo[a.pat[rr]];
@@ -508,7 +571,10 @@ __global__ __launch_bounds__(TB) void k_spmv_pair(PatArgs a, const uint16_t* __r
             sum = sum + tv;
         }
         double y = sum;
-        if (MODE != 0) {
+        if (MODE == 4) {
+            y = lz_sub(sum, lzb, lzhas ? a.xprev[rr] : 0.0, lzhas);
+            d = d + y * a.x[rr];
+        } else if (MODE != 0) {
             const double u = a.shift * a.x[rr];
             y = y - u;
             if (MODE == 2) {
@@ -517,6 +583,15 @@ __global__ __launch_bounds__(TB) void k_spmv_pair(PatArgs a, const uint16_t* __r
             }
         }
         a.y[rr] = y;
+    }
+    return d;
+    };
+    const double lzd = rows();
+    (void)lzd;
+    if constexpr (MODE == 4) {
+        __shared__ double ws[TB / 64];
+        const double sb = lz_block_sum<TB / 64>(lzd, ws);
+        if (tid == 0) a.dotp[blockIdx.x] = sb;
     }
 }
 
@@ -609,7 +684,8 @@ constexpr size_t kPatLdsMax = 64 * 1024;
 
 // the pair kernel needs 16-B aligned columns, rows <= 8 entries and an LDS-sized pair table
 bool spmv_pat_pair_path(const PatArgs& a) {
-    const bool al16 = (((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)(a.mode == 2 ? a.xprev : nullptr)) & 15) == 0;
+    const bool al16 =
+        (((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)(a.mode == 2 || a.mode == 4 ? a.xprev : nullptr)) & 15) == 0;
     const size_t lds2 = (size_t)a.npent * 20 + (size_t)a.nppat * 8 + 16;
     return a.ppat && al16 && a.maxlen <= 8 && lds2 <= kPatLdsMax;
 }
@@ -961,6 +1037,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAL_SPMV_WP
     extern __shared__ __attribute__((aligned(16))) double lds_plane[];
     CAL_PLANE_MARCH(pm, a.x, Z)
     const double2 xp0 = pm.ld2((pm.z0 - 1) * pm.P + pm.xy0 + 2 * pm.tid);
+    // MODE 4 (see lz_sub): the lane's y .* x over its planes, one block sum at the end
+    const bool lzhas = MODE == 4 && a.xprev && a.pb2;
+    const double lzb = lzhas ? sqrt(*a.pb2) : 0.0;
+    const double* lzq = lzhas ? a.xprev : a.x;
+    double lzd = 0.0;
     auto run = [&](auto fullc) {
         constexpr bool FULL = decltype(fullc)::value;
         pm.march(xp0, [&](int j, auto bc, const double2& xp, const double2& xc, const double2& xn, unsigned wm) {
@@ -969,7 +1050,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAL_SPMV_WP
             const bool v0 = FULL || (pm.in0 && r < pm.n), v1 = FULL || (pm.in1 && r + 1 < pm.n);
             double y0, y1;
             pm.template sums<true, B>(pm.z0 + j, xp, xc, xn, wm, y0, y1);
-            if (MODE != 0) {
+            if (MODE == 4) {
+                double2 q;
+                if (FULL) q = ld16g(lzq + r);
+                else q = make_double2(lzq[v0 ? r : 0], lzq[v1 ? r + 1 : 0]);
+                y0 = lz_sub(y0, lzb, q.x, lzhas);
+                y1 = lz_sub(y1, lzb, q.y, lzhas);
+                // rows outside the matrix contribute 0 (their xc is not x)
+                const double d0 = y0 * xc.x, d1 = y1 * xc.y;
+                lzd = lzd + (v0 ? d0 : 0.0);
+                lzd = lzd + (v1 ? d1 : 0.0);
+            } else if (MODE != 0) {
                 const double u0 = a.shift * xc.x, u1 = a.shift * xc.y;
                 y0 = y0 - u0;
                 y1 = y1 - u1;
@@ -988,6 +1079,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAL_SPMV_WP
     };
     if (pm.full) run(std::true_type{});
     else run(std::false_type{});
+    if constexpr (MODE == 4) {
+        // the march's last step ended with a block barrier: its windows are free
+        const double sb = lz_block_sum<4>(lzd, pm.win);
+        if (pm.tid == 0) a.dotp[blockIdx.x] = sb;
+    }
 }
 
 // the plane march applies to a whole single slab (pat_args sets the tables)
@@ -1087,6 +1183,13 @@ static hipError_t launch_spmv_planes(const PatArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// MODE 4's grid (launch_pat_mode's): one y'x partial per block
+int spmv_pat_lanczos_blocks(const PatArgs& a) {
+    if (planes_ok(a)) return planes_blocks(a, spmv_planes_z(a));
+    if (spmv_pat_pair_path(a)) return (int)(((a.n + 1) / 2 + 511) / 512);
+    return 0;
+}
+
 template <int MODE>
 static hipError_t launch_pat_mode(const PatArgs& a, hipStream_t st) {
     if (planes_ok(a)) return launch_spmv_planes<MODE>(a, st);
@@ -1117,6 +1220,9 @@ static hipError_t launch_pat_mode(const PatArgs& a, hipStream_t st) {
 #undef CAL_PR
         return hipGetLastError();
     }
+    if constexpr (MODE == 4) {
+        return hipErrorInvalidValue;  // the row kernels stay unfused (spmv_pat_lanczos_blocks: 0)
+    } else {
     if (lds <= kPatLdsMax) {
         const int blocks = a.nblk < 2048 ? a.nblk : 2048;
         const int cpb = (a.nblk + blocks - 1) / blocks;
@@ -1145,6 +1251,7 @@ static hipError_t launch_pat_mode(const PatArgs& a, hipStream_t st) {
         default: hipLaunchKernelGGL((k_spmv_pat<MODE, 32>), g, b, 0, st, a); break;
     }
     return hipGetLastError();
+    }
 }
 
 // blocks of the pair residual launch (0: the pair path does not apply)
@@ -1527,6 +1634,10 @@ hipError_t launch_spmv_pat(const PatArgs& a, hipStream_t st) {
     switch (a.mode) {
         case 0: return launch_pat_mode<0>(a, st);
         case 1: return launch_pat_mode<1>(a, st);
+        case 4:
+            // the fused Lanczos mode exists on the plane march and the pair kernel
+            if (!a.dotp || a.gap != 0 || spmv_pat_lanczos_blocks(a) <= 0) return hipErrorInvalidValue;
+            return launch_pat_mode<4>(a, st);
         default: return launch_pat_mode<2>(a, st);
     }
 }
@@ -4095,6 +4206,19 @@ hipError_t launch_pro_step(double* r, const double* qprev, const double* pb_prev
     double* pb = part + nb;  // beta^2 partials
     hipLaunchKernelGGL(k_pro_dot, dim3(nb), dim3(256), 0, st, r, qprev, pb_prev, q, n, pa);
     hipLaunchKernelGGL(k_pro_update, dim3(nb), dim3(256), 0, st, r, q, pa, nb, d_alpha, n, pb);
+    hipLaunchKernelGGL(k_pro_div, dim3(redvec_blocks(n)), dim3(256), 0, st, qnext, r, pb, nb, d_beta2, n);
+    return hipGetLastError();
+}
+
+// The tail of a fused Lanczos step (SpMV mode 4 left r = A q - beta qprev and
+// `np` partials of r'q in pa): k_pro_update sums them in k_reduce's order ->
+// *d_alpha, r -= alpha q, partials of r'r into pb (dot_blocks(n) doubles);
+// k_pro_div sums those -> *d_beta2, qnext = r / sqrt(beta2).  Unchanged kernels.
+hipError_t launch_pro_tail(double* r, const double* q, double* qnext, int64_t n, const double* pa, int np, double* pb,
+                           double* d_alpha, double* d_beta2, hipStream_t st) {
+    if (n <= 0 || np < 1) return hipErrorInvalidValue;
+    const int nb = dot_blocks(n);
+    hipLaunchKernelGGL(k_pro_update, dim3(nb), dim3(256), 0, st, r, q, pa, np, d_alpha, n, pb);
     hipLaunchKernelGGL(k_pro_div, dim3(redvec_blocks(n)), dim3(256), 0, st, qnext, r, pb, nb, d_beta2, n);
     return hipGetLastError();
 }

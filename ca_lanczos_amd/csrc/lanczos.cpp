@@ -227,6 +227,8 @@ static int normest_dev(cal_ctx* c, double* out) {
     }
 }
 
+int normest_run(cal_ctx* c, double* out) { return normest_dev(c, out); }
+
 // ---- normest on its own stream (one rank) ----------------------------------
 // The same iteration as normest_dev -- the same kernels in the same order, so
 // the same e to the bit -- enqueued on the context's normest stream in chunks
@@ -1574,6 +1576,19 @@ int cal_lanczos_end(cal_ctx* c) {
 int cal_compute_ritz_rnorm(cal_ctx* c, const double* Q, int k, const double* Vp, const double* d, double* rn) {
     if (!c || !Q || !Vp || !d || !rn || k < 1) return CAL_ERR_ARG;
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    const int64_t n = c->A.n_local, ld = c->A.ld;
+    CAL_TRY(ensure_work(c, 2 * k, ld));
+    double* Qd = work_col(c, 0) + c->A.lpad;
+    CAL_HIP(c, hipMemcpy2DAsync(Qd, ld * sizeof(double), Q, n * sizeof(double), n * sizeof(double), k,
+                                hipMemcpyHostToDevice, c->stream));
+    return ritz_rnorm_dev(c, Qd, k, Vp, d, rn);
+}
+
+}  // extern "C"
+
+// the same for Q already on the device (k columns at Qd, leading dimension
+// A.ld, local origin; not work columns [k, 2k), which hold X)
+int cal::ritz_rnorm_dev(cal_ctx* c, const double* Qd, int k, const double* Vp, const double* d, double* rn) {
     for (int i = 0; i < k; ++i)
         if (!std::isfinite(d[i])) return set_error(c, CAL_ERR_ARG, "compute_ritz_rnorm: non-finite eigenvalue");
     const int64_t n = c->A.n_local, ld = c->A.ld;
@@ -1581,10 +1596,7 @@ int cal_compute_ritz_rnorm(cal_ctx* c, const double* Q, int k, const double* Vp,
     for (int j = 0; j < k; ++j) pairs.push_back({d[j], 0.0, j, -1});
     matlab_sort_desc(pairs, false);
     CAL_TRY(ensure_work(c, 2 * k, ld));
-    double* Qd = work_col(c, 0) + c->A.lpad;
     double* X = work_col(c, k) + c->A.lpad;
-    CAL_HIP(c, hipMemcpy2DAsync(Qd, ld * sizeof(double), Q, n * sizeof(double), n * sizeof(double), k,
-                                hipMemcpyHostToDevice, c->stream));
     const int nbp = spmv_resid_pair_multi_blocks(c);
     const int nbr = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + 255) / 256));
     const size_t npart = (size_t)2 * k * std::max(nbp, nbr);
@@ -1645,6 +1657,8 @@ int cal_compute_ritz_rnorm(cal_ctx* c, const double* Q, int k, const double* Vp,
     };
     return fin(go());
 }
+
+extern "C" {
 
 int cal_ca_lanczos(cal_ctx* c, const double* r, int s, int iter, const char* basis, const char* orth,
                    int diagnostics, double* T, double* Q, double* rn, double* oe, int* reorth_flags,

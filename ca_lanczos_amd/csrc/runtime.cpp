@@ -738,6 +738,60 @@ int spmv_dev(cal_ctx* c, const double* x, double* y, int mode, double shift, dou
     return 0;
 }
 
+// The fused Lanczos step (mode 4): y = A x - sqrt(*pb2) xprev (xprev / pb2
+// null: y = A x, the bits of mode 0) and one partial of y'x per block in
+// dotp.  One rank.  spmv_lanczos_parts: the number of partials (the launch's
+// grid), 0 when the matrix sits on the unfused row-pattern kernels.
+static SpmvArgs csr_args(const cal_ctx* c, const double* x, double* y, int mode) {
+    SpmvArgs a;
+    a.rowptr = c->A.rowptr;
+    a.col = c->A.col;
+    a.val = c->A.val;
+    a.blk = c->A.blk;
+    a.nblk = c->A.nblk;
+    a.x = x;
+    a.y = y;
+    a.xprev = nullptr;
+    a.shift = 0.0;
+    a.im2 = 0.0;
+    a.mode = mode | (c->A.nit << 8);
+    a.nt = (int64_t)12 * c->A.nnz > ((int64_t)256 << 20) ? 1 : 0;
+    return a;
+}
+
+int spmv_lanczos_parts(const cal_ctx* c, const double* x, const double* xprev, double* y) {
+    const DevMatrix& A = c->A;
+    if (!c->has_A || (c->comm && c->comm->nranks > 1)) return 0;
+    if (!A.use_pat) return spmv_lanczos_blocks(csr_args(c, x, y, 4));
+    return spmv_pat_lanczos_blocks(pat_args(A, A.ext_off, A.n_local, x, y, 4, 0.0, 0.0, xprev));
+}
+
+int spmv_lanczos_dev(cal_ctx* c, const double* x, const double* xprev, const double* pb2, double* y, double* dotp) {
+    const DevMatrix& A = c->A;
+    if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    if (spmv_lanczos_parts(c, x, xprev, y) <= 0 || !dotp)
+        return set_error(c, CAL_ERR_ARG, "spmv_lanczos_dev: no fused Lanczos mode for this matrix");
+    const bool has = xprev && pb2;
+    c->stat_spmv_rows += A.n_local;
+    if (A.use_pat) {
+        PatArgs p = pat_args(A, A.ext_off, A.n_local, x, y, 4, 0.0, 0.0, has ? xprev : nullptr);
+        p.pb2 = has ? pb2 : nullptr;
+        p.dotp = dotp;
+        const int t = timer_begin(c, 0, pat_spmv_bytes(A, A.n_local, has ? 2 : 0));
+        CAL_HIP(c, launch_spmv_pat(p, c->stream));
+        timer_end(c, t);
+        return 0;
+    }
+    SpmvArgs a = csr_args(c, x, y, 4);
+    a.xprev = has ? xprev : nullptr;
+    a.pb2 = has ? pb2 : nullptr;
+    a.dotp = dotp;
+    const int t = timer_begin(c, 0, 12.0 * A.nnz + 20.0 * A.n_local + 4.0 + (has ? 8.0 * A.n_local : 0.0));
+    CAL_HIP(c, launch_spmv(a, c->stream));
+    timer_end(c, t);
+    return 0;
+}
+
 // CA matrix powers: after one halo exchange of q's s-deep
 // ghost zone, power j (1-based) is valid on global rows [row0 - (s-j) bl,
 // row1 + (s-j) br) -- it reads power j-1 one band further out -- so power s
@@ -903,6 +957,7 @@ int cal_create(int device, cal_ctx** out) {
 
 void cal_lanczos_free_state(cal_ctx* c);  // lanczos.cpp
 void cal_prop_free_state(cal_ctx* c);     // prop.cpp
+void cal_std_lanczos_free_state(cal_ctx* c);  // lanczos_std.cpp
 
 void cal_destroy(cal_ctx* c) {
     if (!c) return;
@@ -910,6 +965,7 @@ void cal_destroy(cal_ctx* c) {
     hipStreamSynchronize(c->stream);
     if (c->nest_stream) hipStreamSynchronize(c->nest_stream);
     cal_prop_free_state(c);
+    cal_std_lanczos_free_state(c);
     cal_lanczos_free_state(c);
     cal::comm_destroy(c);
     free_matrix(c);

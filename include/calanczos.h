@@ -347,6 +347,53 @@ int cal_ca_lanczos_prop(cal_ctx* ctx, int64_t n, const double* r_re, const doubl
                         double tol, const char* basis, const double* eigest, int neig, int adaptive, double* T,
                         double* Q_re, double* Q_im, int* lsteps);
 
+/* ---- standard Lanczos: [T,Q,ritz_rnorm,orth_err] = lanczos(A,r,maxiter,orth) */
+/* lanczos.m:18-311, device-resident, the other half of the reference's
+ * ca_lanczos / lanczos comparisons.  orth is "local", "full", "periodic" or
+ * "selective" (anything else: CAL_ERR_ARG, as is maxiter < 1 or > n).  One
+ * Lanczos step is the fused SpMV mode (y = A q_j - beta_{j-1} q_{j-1} with the
+ * block partials of y'q_j) and two vector kernels; alpha and beta^2 stay on the
+ * device, so "local" and "full" enqueue their steps without a host round trip.
+ * "periodic" and "selective" read alpha_j, beta_j on the host every step.  In
+ * "periodic" the reference's window Q(:,j-5:j+1) is clamped to start at column
+ * 1 for j <= 6 (the reference indexes out of range there) and the earlier
+ * block is then empty.  One rank only (CAL_ERR_UNSUPPORTED with a communicator
+ * of more ranks). */
+typedef struct cal_std_lanczos_info {
+    int steps;           /* Lanczos steps kept (columns of T)                   */
+    int breakdown;       /* 1: beta_j == 0 or non-finite; steps is cut before it */
+    int fused;           /* 1: the fused SpMV mode ran, 0: MODE 0 + k_pro_dot   */
+    int n_orth_breaks;   /* periodic: reorthogonalisations; selective: QR rebuilds */
+    int n_ritz_locked;   /* selective                                           */
+    double norm_A;       /* normest(A) (periodic / selective)                   */
+    double loop_ms, diag_ms;
+} cal_std_lanczos_info;
+
+/* One call: T is m x m (ld m, m = maxiter), its leading steps x steps block
+ * filled and the rest zero; Q n x m (may be NULL; columns past steps zero); rn
+ * m x m, row j = step j (ld m; may be NULL); oe m entries (may be NULL); rn /
+ * oe are written with diagnostics != 0 only.  A beta_j that is not finite and
+ * positive cuts steps to j and returns CAL_WARN_BREAKDOWN. */
+int cal_lanczos(cal_ctx* ctx, const double* r, int maxiter, const char* orth, int diagnostics, double* T, double* Q,
+                double* rn, double* oe, cal_std_lanczos_info* info);
+/* Step-wise.  keep_Q = 0 ("local" only, else CAL_ERR_ARG) keeps a ring of
+ * three columns: O(n) memory, the same T to the bit, no get_Q, no diagnostics. */
+int cal_std_lanczos_begin(cal_ctx* ctx, const double* r, int maxiter, const char* orth, int keep_Q);
+/* nsteps more steps (CAL_ERR_ARG past maxiter).  "local" / "full" without
+ * diagnostics only enqueue: a breakdown shows in cal_std_lanczos_get. */
+int cal_std_lanczos_step(cal_ctx* ctx, int nsteps, int diagnostics);
+/* alpha, beta (steps entries each; beta_j of a breakdown is stored as 0), rn
+ * (ld maxiter), oe; every pointer may be NULL.  Waits for the enqueued steps. */
+int cal_std_lanczos_get(cal_ctx* ctx, double* alpha, double* beta, double* rn, double* oe, cal_std_lanczos_info* info);
+int cal_std_lanczos_get_Q(cal_ctx* ctx, int64_t col0, int ncols, double* Q);
+int cal_std_lanczos_end(cal_ctx* ctx);
+/* The fused kernel on host data: y = A x - sqrt(beta2) xprev (xprev may be
+ * NULL: y = A x, the bits of cal_spmv), *dot = y'x summed in a fixed order.
+ * CAL_ERR_UNSUPPORTED when the matrix sits on an SpMV kernel without the mode. */
+int cal_spmv_lanczos(cal_ctx* ctx, const double* x, const double* xprev, double beta2, double* y, double* dot);
+/* *fused = 1 when the context's matrix takes the fused mode */
+int cal_spmv_lanczos_fused(cal_ctx* ctx, int* fused);
+
 /* ---- multi-GPU (row slabs, RCCL over xGMI) ------------------------------ */
 /* 128-byte RCCL unique id; broadcast it out of band (e.g. torch.distributed). */
 int cal_comm_unique_id(void* id128);
