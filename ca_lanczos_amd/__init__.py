@@ -35,6 +35,7 @@ from .api import (  # noqa: F401
     projectAndNormalize_ex,
     restarted_ca_lanczos,
     impl_restarted_ca_lanczos,
+    split_analyze,
     tsqr,
 )
 from . import matrices  # noqa: F401

@@ -138,6 +138,17 @@ class Context:
         check(self.h, lib.cal_spmv_plane_info(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
 
+    def spmv_split_info(self):
+        """(on, plane stride P, in-plane reach H, neg1) of the diagonal-split
+        format (``spmv_format="split"``, or "auto" on a grid Hamiltonian K +
+        diag(V)); (False, 0, 0, False) when the matrix does not run there.
+        ``spmv_format()`` reports "csr" for such a matrix: only its SpMV takes
+        the split kernels."""
+        on, P, H, ng = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
+        check(self.h, lib.cal_spmv_split_info(self.h, ctypes.byref(on), ctypes.byref(P), ctypes.byref(H),
+                                              ctypes.byref(ng)))
+        return bool(on.value), P.value, H.value, bool(ng.value)
+
     def close(self):
         if self.h:
             lib.cal_destroy(self.h)
@@ -363,6 +374,24 @@ class Context:
         f = ctypes.c_int()
         check(self.h, lib.cal_spmv_lanczos_fused(self.h, ctypes.byref(f)), "spmv_lanczos_fused")
         return bool(f.value)
+
+
+def split_analyze(A):
+    """Whether A qualifies for the diagonal-split SpMV format (a uniform 5- or
+    7-point stencil plus a per-row diagonal, ``grid_hamiltonian``): ``(P, H,
+    neg1)`` (plane stride, in-plane reach, every off-diagonal is -1) or
+    ``None``.  Host only (cal_split_analyze: the upload's own analysis)."""
+    A = to_csr(A)
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("A must be square")
+    rowptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
+    col = np.ascontiguousarray(A.indices, dtype=np.int32)
+    val = np.ascontiguousarray(A.data, dtype=np.float64)
+    P, H, ng = ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
+    ok = lib.cal_split_analyze(A.shape[0], rowptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                               col.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(val), ctypes.byref(P),
+                               ctypes.byref(H), ctypes.byref(ng))
+    return (P.value, H.value, bool(ng.value)) if ok else None
 
 
 def _std_orth(orth):

@@ -148,6 +148,14 @@ struct PatArgs {
     // mode 4, as SpmvArgs (plane march and pair kernel; one range)
     const double* pb2 = nullptr;
     double* dotp = nullptr;
+    // the diagonal-split format (launch_spmv_dsplit): the per-row diagonal, n
+    // entries, +0.0 where the row stores none; the slots, their uniform values
+    // (cval[middle] unused), rowmask and wavemask describe the stencil
+    const double* diag = nullptr;
+    // its mode 4 (kernels.hip k_dsplit_dot): the sums of the 64-row groups
+    // (n / 64 + 1) and the y x of the rows whose group straddles two blocks (n)
+    double* gsum = nullptr;
+    double* dprod = nullptr;
 };
 constexpr int kPairSplit = 0xFFFF;
 // the plane march: rows of a plane per block (4 waves x 64 lanes x 2 rows)
@@ -208,6 +216,23 @@ struct DevMatrix {
     double cval[8] = {};
     int64_t plane_P = 0;
     int plane_H = 0;
+    // The diagonal-split format (a whole single slab): a uniform
+    // stencil of 5 or 7 canonical slots -P .. -1, 0, +1 .. +P and a per-row
+    // diagonal, H = K + diag(V).  use_pat stays false and the CSR arrays are
+    // uploaded as for any CSR matrix: only the SpMV dispatch (modes 0, 1, 2
+    // and 4) reads these fields and runs the plane march with DG
+    bool use_dsplit = false;
+    int ds_L = 0;                  // slots
+    int ds_slot[8] = {};
+    double ds_cval[8] = {};        // the slots' uniform values (the middle one: a placeholder)
+    int64_t ds_P = 0;
+    int ds_H = 0;
+    bool ds_neg1 = false;          // every off-diagonal is -1
+    uint8_t* ds_rowmask = nullptr;   // n + 8 bytes (as rowmask)
+    uint32_t* ds_wavemask = nullptr; // as wavemask
+    double* ds_diag = nullptr;       // n + 2 doubles
+    double* ds_gsum = nullptr;       // PatArgs::gsum
+    double* ds_dprod = nullptr;      // PatArgs::dprod
     // halo plan (distributed); ghost entries grouped by owning peer
     std::vector<int> peers;              // neighbour ranks
     std::vector<int64_t> recv_off;       // ghost destination per peer, relative to the local origin
@@ -231,6 +256,11 @@ hipError_t launch_spmv_pat(const PatArgs& a, hipStream_t st);
 // Lanczos mode -- the row-pattern kernels k_spmv_pat / k_spmv_pat_lds)
 int spmv_lanczos_blocks(const SpmvArgs& a);
 int spmv_pat_lanczos_blocks(const PatArgs& a);
+// the diagonal-split format: the plane march with the streamed diagonal
+// (modes 0, 1, 2, 4; hipErrorInvalidValue for anything it is not built for);
+// spmv_dsplit_blocks: mode 4's number of y'x partials (one per 256 rows)
+hipError_t launch_spmv_dsplit(const PatArgs& a, hipStream_t st);
+int spmv_dsplit_blocks(const PatArgs& a);
 // C (wa x wb, column-major ldc = 16*ceil(wa/16)) partials; see kernels.hip.
 struct GramPlan {
     int nta;    // A tiles of 16 columns
@@ -529,7 +559,7 @@ struct cal_ctx {
     std::vector<CalTimerRec> timers;
     std::vector<hipEvent_t> event_pool;
 
-    int spmv_format = 0;  // 0 auto, 1 CSR, 2 row-pattern (applies at the next set_matrix)
+    int spmv_format = 0;  // 0 auto, 1 CSR, 2 row-pattern, 3 diagonal split (applies at the next set_matrix)
     int mpk_depth_req = 8;
     // schedule of the last powers_dev call (cal_mpk_schedule): 0 one halo
     // exchange per SpMV, 1 one deep exchange, 2 deep exchange on the RCCL

@@ -728,8 +728,25 @@ bool spmv_pat_pair_path(const PatArgs& a) {
 // the value cval[e], as in the Laplacians): the keys are the rows' slot mask
 // bytes.  KM = 1 / 2: the keys are the rows' pattern ids (1 / 2 B) into the
 // LDS value / mask tables.
-template <int MAXLEN, int KM, bool LN, bool NEG1>
+// DG (the diagonal-split format, DESIGN.md §3: a uniform stencil plus a
+// per-row diagonal, H = K + diag(V)): the offset-0 slot's coefficients are
+// the lane's two entries of the streamed vector diag (+0.0 where the row
+// stores no diagonal entry, whose mask bit is clear), every other slot is as
+// with KM = 0.  The lane's diag pair of plane z0 + j is loaded at the top of
+// step j, ahead of the prefetch of plane z0 + j + 2 (loads return in order:
+// the wait for it does not wait for the prefetch), one 16-B load in a full
+// block and two guarded 8-B loads in a partial one.
+#ifndef CAL_DSPLIT_NT
+// diag streams once per SpMV: non-temporal loads.  Against plain loads on the
+// 215^3 Hamiltonian (profiles/dsplit/ab_*): the fused Lanczos loop 117.8-120.0
+// against 122.3-123.5 us per vector, the CA loop and the propagator unchanged;
+// only the back-to-back SpMV, whose 250 MB then nearly fit the Infinity Cache,
+// is faster with plain loads (39.2-39.4 against 42.3-42.5 us)
+#define CAL_DSPLIT_NT 1
+#endif
+template <int MAXLEN, int KM, bool LN, bool NEG1, bool DG = false>
 struct PlaneMarch {
+    static_assert(!DG || (KM == 0 && LN), "the diagonal split runs on uniform slots with the offsets -1, 0, +1");
     static constexpr int KB = KM == 2 ? 2 : 1;                  // key bytes per row
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     static constexpr int L2 = (MAXLEN + 1) & ~1;                // table row stride (16-B reads)
@@ -759,6 +776,8 @@ struct PlaneMarch {
     double2 st0, st1;   // the prefetched plane's own and halo pair (registers)
     uint32_t kst[KR];
     uint32_t wmv;       // the prefetched plane's wave masks (uniform)
+    const double* dgp;  // DG: the diagonal (n entries)
+    double2 dg;         // DG: the lane's diag pair of the step's plane
 
     __device__ static __amdgpu_buffer_rsrc_t rsrc(const void* p, int64_t bytes) {
         const uint64_t pl = (uint64_t)(uintptr_t)p;
@@ -836,6 +855,30 @@ struct PlaneMarch {
                             __builtin_bit_cast(double, ((uint64_t)w.w << 32) | w.z));
     }
     __device__ double2 ld2(int row) const { return ld16(row * 8); }
+    // DG: the lane's diag pair of plane z (8-B aligned on the odd planes of an
+    // odd P); rows outside the matrix read entry 0 and are never stored
+    __device__ static double ldd(const double* p) {
+#if CAL_DSPLIT_NT
+        return __builtin_nontemporal_load(p);
+#else
+        return *p;
+#endif
+    }
+    template <bool FULL>
+    __device__ void load_diag(int z) {
+        const int r = z * P + xy0 + 2 * tid;
+        if (FULL) {
+#if CAL_DSPLIT_NT
+            typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+            const d2u v = __builtin_nontemporal_load(reinterpret_cast<const d2u*>(dgp + r));
+            dg = make_double2(v.x, v.y);
+#else
+            __builtin_memcpy(&dg, dgp + r, 16);
+#endif
+        } else {
+            dg = make_double2(ldd(dgp + (in0 && r < n ? r : 0)), ldd(dgp + (in1 && r + 1 < n ? r + 1 : 0)));
+        }
+    }
     // issue plane z's loads into registers: the lane's own pair, its halo pair
     // (lanes past H load lane H - 1's again and do not store it), the keys, the
     // waves' masks.
@@ -871,9 +914,10 @@ struct PlaneMarch {
     // lane's pair of planes j - 1 / j / j + 1, wm the wave's mask), then the
     // prefetched plane goes into buffer (B + 2) % 3 and register set
     // (B + 2) % 3 (plane j - 1's, no longer needed), and the block syncs.
-    template <int B, typename F>
+    template <int B, bool FULL, typename F>
     __device__ void step(int j, double2 (&r)[3], unsigned (&w)[3], F&& f) {
         constexpr int BP = (B + 2) % 3, BN = (B + 1) % 3;
+        if constexpr (DG) load_diag<FULL>(z0 + j);
         if (j + 2 <= zend) load(z0 + j + 2);
         f(j, std::integral_constant<int, B>{}, r[BP], r[B], r[BN], w[B]);
         // the plane's arithmetic stays ahead of the stores, which wait for
@@ -894,7 +938,8 @@ struct PlaneMarch {
     // prologue's stores have waited for the loads (loads return in order), so
     // the loop's first use does not wait for the prefetch issued at the top of
     // the step.
-    template <typename F>
+    // FULL (DG only): every row pair of the block lies inside the matrix.
+    template <bool FULL = false, typename F>
     __device__ void march(const double2& xp, F&& f) {
         double2 r[3];
         unsigned w[3];
@@ -911,9 +956,9 @@ struct PlaneMarch {
         asm volatile("" : "+v"(r[0].x), "+v"(r[0].y), "+v"(r[1].x), "+v"(r[1].y), "+v"(r[2].x), "+v"(r[2].y));
         __syncthreads();
         for (int j = 0; j < zend; j += 3) {
-            step<0>(j, r, w, f);
-            if (j + 1 < zend) step<1>(j + 1, r, w, f);
-            if (j + 2 < zend) step<2>(j + 2, r, w, f);
+            step<0, FULL>(j, r, w, f);
+            if (j + 1 < zend) step<1, FULL>(j + 1, r, w, f);
+            if (j + 2 < zend) step<2, FULL>(j + 2, r, w, f);
         }
     }
     // the lane's two row keys of plane z (buffer B)
@@ -982,8 +1027,8 @@ struct PlaneMarch {
                 }
                 continue;
             }
-            const double c0 = KM == 0 ? cv[e] : s_rz[k0 * L2 + e];
-            const double c1 = KM == 0 ? cv[e] : s_rz[k1 * L2 + e];
+            const double c0 = DG && e == MID ? dg.x : (KM == 0 ? cv[e] : s_rz[k0 * L2 + e]);
+            const double c1 = DG && e == MID ? dg.y : (KM == 0 ? cv[e] : s_rz[k1 * L2 + e]);
             const double t0 = c0 * v.x, t1 = c1 * v.y;
             if (e == 0 && !Z0) {
                 y0 = t0;
@@ -999,12 +1044,13 @@ struct PlaneMarch {
     }
 };
 
-#define CAL_PLANE_MARCH(PM, XPTR, Zv)                                                                          \
-    PlaneMarch<MAXLEN, KM, LN, NEG1> PM(a.plane_P, a.plane_H, a.n, a.ld, XPTR,                                 \
-                                        KM == 0 ? (const void*)a.rowmask                                      \
-                                                : (KM == 1 ? (const void*)a.rowkey8 : (const void*)a.pat),    \
-                                        a.wavemask, a.rzval, a.rzmask, a.npat, lds_plane,                     \
-                                        xcd_remap(blockIdx.x, gridDim.x), Zv);                                \
+#define CAL_PLANE_MARCH(PM, XPTR, Zv) CAL_PLANE_MARCH_DG(PM, XPTR, Zv, false)
+#define CAL_PLANE_MARCH_DG(PM, XPTR, Zv, DGv)                                                                  \
+    PlaneMarch<MAXLEN, KM, LN, NEG1, DGv> PM(a.plane_P, a.plane_H, a.n, a.ld, XPTR,                            \
+                                             KM == 0 ? (const void*)a.rowmask                                 \
+                                                     : (KM == 1 ? (const void*)a.rowkey8 : (const void*)a.pat), \
+                                             a.wavemask, a.rzval, a.rzmask, a.npat, lds_plane,                \
+                                             xcd_remap(blockIdx.x, gridDim.x), Zv);                           \
     _Pragma("unroll") for (int e_ = 0; e_ < MAXLEN; ++e_) {                                                   \
         PM.ps[e_] = a.pslot[e_];                                                                              \
         PM.cv[e_] = a.cval[e_];                                                                               \
@@ -1032,19 +1078,125 @@ __device__ __forceinline__ double2 ld16g(const double* p) {
 #define CAL_RESID_WPE 5
 #endif
 
-template <int MODE, int MAXLEN, int Z, int KM, bool LN, bool NEG1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAL_SPMV_WPE))) void k_spmv_planes(PatArgs a) {
+// DG, MODE 4: y'x in the CSR kernel's own order, so that alpha -- and with it a
+// whole standard Lanczos run -- has the bits of the same matrix on CSR.  There
+// (k_spmv; rows of at most 8 entries make every row block 256 consecutive
+// rows) thread t of block b holds y x of row 256 b + t, each wave sums its 64
+// rows (wave_sum) and the block adds the four wave sums in order.  Here the
+// lanes put their products of a plane into LDS in row order (two buffers in
+// turn: a plane's products are summed during the next step, after the step's
+// barrier); every 64-row group 64 k .. 64 k + 63 that lies inside the block's
+// rows of that plane is summed by one wave with the same wave_sum into
+// gsum[k]; the rows of the groups that straddle two blocks or two planes go
+// to dprod[row], and k_dsplit_dot finishes them and forms the CSR blocks'
+// partials in lz_block_sum's order.
+__device__ __forceinline__ bool dsplit_group_inside(int k, int R0, int cnt, int n) {
+    return 64 * k >= R0 && min(64 * k + 64, n) <= R0 + cnt;
+}
+// the rows of plane z the block owns: R0 .. R0 + cnt - 1
+__device__ __forceinline__ int dsplit_rows(int z, int P, int xy0, int n, int& R0) {
+    R0 = z * P + xy0;
+    return min(min(kPlaneBlockRows, P - xy0), n - R0);
+}
+// A block's 512 rows of a plane hold at most 8 whole groups, k0 .. k0 + 7: wave
+// w sums groups k0 + w and k0 + w + 4, the two butterflies interleaved (each
+// is wave_sum's own sequence of additions).  One after the other they measured
+// the same (189.3-190.0 against 189.2-191.2 us per Lanczos vector on the 215^3
+// Hamiltonian): the shuffles are not what the row-ordered dot costs.
+__device__ __forceinline__ void dsplit_group_sums(const double* buf, int z, int P, int xy0, int n, double* gsum) {
+    int R0;
+    const int cnt = dsplit_rows(z, P, xy0, n, R0);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ka = ((R0 + 63) >> 6) + wave, kb = ka + 4;
+    const bool ina = 64 * ka < R0 + cnt && dsplit_group_inside(ka, R0, cnt, n);  // wave-uniform
+    const bool inb = 64 * kb < R0 + cnt && dsplit_group_inside(kb, R0, cnt, n);
+    if (!ina && !inb) return;
+    const int ia = 64 * ka + lane - R0, ib = ia + 256;
+    double va = ina && ia < cnt ? buf[ia] : 0.0;
+    double vb = inb && ib < cnt ? buf[ib] : 0.0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ta = __shfl_xor(va, off, 64), tb = __shfl_xor(vb, off, 64);
+        va = va + ta;
+        vb = vb + tb;
+    }
+    if (lane == 0) {
+        if (ina) gsum[ka] = va;
+        if (inb) gsum[kb] = vb;
+    }
+}
+// One wave per CSR row block b (rows 256 b ..): its four groups' sums -- read
+// from gsum, or summed here from dprod by wave_sum's butterfly, the four
+// interleaved -- added in lz_block_sum's order.  (One 256-thread block per row
+// block with a barrier took 25 us for the 38,822 row blocks of the 215^3
+// Hamiltonian.)
+__global__ __launch_bounds__(256) void k_dsplit_dot(const double* __restrict__ gsum, const double* __restrict__ dprod,
+                                                    int n, int P, int nb, double* __restrict__ dotp) {
+    const int lane = threadIdx.x & 63;
+    const int b = 4 * (int)blockIdx.x + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (b >= nb) return;
+    double v[4], g[4];
+    bool inside[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int k = 4 * b + w, row0 = 64 * k;
+        inside[w] = false;
+        v[w] = 0.0;
+        g[w] = 0.0;
+        if (row0 < n) {  // wave-uniform
+            const int z = row0 / P, xyb = (row0 - z * P) / kPlaneBlockRows;
+            int R0;
+            const int cnt = dsplit_rows(z, P, xyb * kPlaneBlockRows, n, R0);
+            inside[w] = dsplit_group_inside(k, R0, cnt, n);
+            if (inside[w]) g[w] = gsum[k];
+            else if (row0 + lane < n) v[w] = dprod[row0 + lane];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        double t[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) t[w] = __shfl_xor(v[w], off, 64);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) v[w] = v[w] + t[w];
+    }
+#pragma unroll
+    for (int w = 0; w < 4; ++w) g[w] = inside[w] ? g[w] : v[w];
+    if (lane == 0) dotp[b] = ((g[0] + g[1]) + g[2]) + g[3];
+}
+
+// DG: the fused Lanczos step (MODE 4) of the 7-slot march at 8 planes per block
+// sits at 93 VGPRs without the diagonal; with the lane's diag pair and the
+// row-ordered dot it spills at 96 (the 5-slot march too: 4 VGPRs), so MODE 4
+// at 8 planes per block is compiled for 4 waves per SIMD (128 VGPRs, no
+// scratch).  Its 34 KB of LDS allow 4 blocks per CU, i.e. 4 waves per SIMD,
+// anyway.  Every other DG instantiation fits 96 (the register
+// table).
+#ifndef CAL_DSPLIT_WPE_M4
+#define CAL_DSPLIT_WPE_M4 4
+#endif
+constexpr int spmv_planes_wpe(int mode, int z, bool dg) {
+    return dg && mode == 4 && z > 2 ? CAL_DSPLIT_WPE_M4 : CAL_SPMV_WPE;
+}
+
+template <int MODE, int MAXLEN, int Z, int KM, bool LN, bool NEG1, bool DG = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(spmv_planes_wpe(MODE, Z, DG))))
+void k_spmv_planes(PatArgs a) {
     extern __shared__ __attribute__((aligned(16))) double lds_plane[];
-    CAL_PLANE_MARCH(pm, a.x, Z)
+    CAL_PLANE_MARCH_DG(pm, a.x, Z, DG)
+    if constexpr (DG) pm.dgp = a.diag;
     const double2 xp0 = pm.ld2((pm.z0 - 1) * pm.P + pm.xy0 + 2 * pm.tid);
     // MODE 4 (see lz_sub): the lane's y .* x over its planes, one block sum at the end
     const bool lzhas = MODE == 4 && a.xprev && a.pb2;
     const double lzb = lzhas ? sqrt(*a.pb2) : 0.0;
     const double* lzq = lzhas ? a.xprev : a.x;
     double lzd = 0.0;
+    // DG: the planes' products in row order (2 x 512 doubles past the march's LDS)
+    double* const lzp = lds_plane + decltype(pm)::lds_bytes(a.npat) / 8;
     auto run = [&](auto fullc) {
         constexpr bool FULL = decltype(fullc)::value;
-        pm.march(xp0, [&](int j, auto bc, const double2& xp, const double2& xc, const double2& xn, unsigned wm) {
+        pm.template march<FULL>(xp0, [&](int j, auto bc, const double2& xp, const double2& xc, const double2& xn,
+                                         unsigned wm) {
             constexpr int B = decltype(bc)::value;
             const int r = (pm.z0 + j) * pm.P + pm.xy0 + 2 * pm.tid;
             const bool v0 = FULL || (pm.in0 && r < pm.n), v1 = FULL || (pm.in1 && r + 1 < pm.n);
@@ -1058,8 +1210,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAL_SPMV_WP
                 y1 = lz_sub(y1, lzb, q.y, lzhas);
                 // rows outside the matrix contribute 0 (their xc is not x)
                 const double d0 = y0 * xc.x, d1 = y1 * xc.y;
-                lzd = lzd + (v0 ? d0 : 0.0);
-                lzd = lzd + (v1 ? d1 : 0.0);
+                if constexpr (DG) {
+                    st16(lzp + (j & 1) * kPlaneBlockRows + 2 * pm.tid, make_double2(v0 ? d0 : 0.0, v1 ? d1 : 0.0));
+                    int R0;
+                    const int cnt = dsplit_rows(pm.z0 + j, pm.P, pm.xy0, pm.n, R0);
+                    if (v0 && !dsplit_group_inside(r >> 6, R0, cnt, pm.n)) a.dprod[r] = d0;
+                    if (v1 && !dsplit_group_inside((r + 1) >> 6, R0, cnt, pm.n)) a.dprod[r + 1] = d1;
+                    if (j > 0)
+                        dsplit_group_sums(lzp + ((j - 1) & 1) * kPlaneBlockRows, pm.z0 + j - 1, pm.P, pm.xy0, pm.n,
+                                          a.gsum);
+                } else {
+                    lzd = lzd + (v0 ? d0 : 0.0);
+                    lzd = lzd + (v1 ? d1 : 0.0);
+                }
             } else if (MODE != 0) {
                 const double u0 = a.shift * xc.x, u1 = a.shift * xc.y;
                 y0 = y0 - u0;
@@ -1079,7 +1242,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAL_SPMV_WP
     };
     if (pm.full) run(std::true_type{});
     else run(std::false_type{});
-    if constexpr (MODE == 4) {
+    if constexpr (MODE == 4 && DG) {
+        // the last plane's products (the march's last step ended with a block barrier)
+        dsplit_group_sums(lzp + ((pm.zend - 1) & 1) * kPlaneBlockRows, pm.z0 + pm.zend - 1, pm.P, pm.xy0, pm.n, a.gsum);
+    } else if constexpr (MODE == 4) {
         // the march's last step ended with a block barrier: its windows are free
         const double sb = lz_block_sum<4>(lzd, pm.win);
         if (pm.tid == 0) a.dotp[blockIdx.x] = sb;
@@ -1188,6 +1354,62 @@ int spmv_pat_lanczos_blocks(const PatArgs& a) {
     if (planes_ok(a)) return planes_blocks(a, spmv_planes_z(a));
     if (spmv_pat_pair_path(a)) return (int)(((a.n + 1) / 2 + 511) / 512);
     return 0;
+}
+
+// ---- the diagonal-split format (PatArgs::diag): the plane march with DG ----
+// Instantiated for uniform slots with the offsets -1, 0, +1 in the middle
+// (KM = 0, LN), 5 and 7 slots, with and without NEG1, both Z and the modes
+// 0, 1, 2 and 4; the host analysis (runtime.cpp split_analyze) admits no
+// other matrix.
+static bool dsplit_ok(const PatArgs& a) {
+    return a.diag && a.rowmask && a.wavemask && a.cuniform && a.pcanon && a.plane_P >= 256 && a.plane_H <= 256 &&
+           (a.pmaxlen == 5 || a.pmaxlen == 7) && planes_ln(a) && a.pslot[0] == -a.plane_P &&
+           a.pslot[a.pmaxlen - 1] == a.plane_P && a.gap == 0 && a.xlo == 0 && a.n > 0 && a.ld >= a.n + 2 &&
+           a.ld < ((int64_t)1 << 28);
+}
+
+// MODE 4's y'x partials: one per 256 rows, as the CSR kernel's (k_dsplit_dot)
+int spmv_dsplit_blocks(const PatArgs& a) {
+    return dsplit_ok(a) && a.gsum && a.dprod ? (int)((a.n + 255) / 256) : 0;
+}
+
+template <int MODE>
+static hipError_t launch_dsplit_mode(const PatArgs& a, hipStream_t st) {
+    const size_t lds = PlaneMarch<8, 0, false, false>::lds_bytes(0) + (MODE == 4 ? 2 * kPlaneBlockRows * 8 : 0);
+    const int z = spmv_planes_z(a);
+    dim3 g((unsigned)planes_blocks(a, z)), b(256);
+    auto go = [&](auto ml, auto ng) {
+        constexpr int ML = decltype(ml)::value;
+        constexpr bool NEG1 = decltype(ng)::value;
+        if (z == kSpmvPlanes)
+            hipLaunchKernelGGL((k_spmv_planes<MODE, ML, kSpmvPlanes, 0, true, NEG1, true>), g, b, lds, st, a);
+        else hipLaunchKernelGGL((k_spmv_planes<MODE, ML, 2, 0, true, NEG1, true>), g, b, lds, st, a);
+    };
+    const bool ng = planes_neg1(a);
+    if (a.pmaxlen == 5) {
+        if (ng) go(std::integral_constant<int, 5>{}, std::true_type{});
+        else go(std::integral_constant<int, 5>{}, std::false_type{});
+    } else {
+        if (ng) go(std::integral_constant<int, 7>{}, std::true_type{});
+        else go(std::integral_constant<int, 7>{}, std::false_type{});
+    }
+    if (MODE == 4) {
+        const int nb = spmv_dsplit_blocks(a);
+        hipLaunchKernelGGL(k_dsplit_dot, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, a.gsum, a.dprod, (int)a.n,
+                           (int)a.plane_P, nb, a.dotp);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_spmv_dsplit(const PatArgs& a, hipStream_t st) {
+    if (!dsplit_ok(a)) return hipErrorInvalidValue;
+    switch (a.mode) {
+        case 0: return launch_dsplit_mode<0>(a, st);
+        case 1: return launch_dsplit_mode<1>(a, st);
+        case 2: return a.xprev ? launch_dsplit_mode<2>(a, st) : hipErrorInvalidValue;
+        case 4: return a.dotp && a.gsum && a.dprod ? launch_dsplit_mode<4>(a, st) : hipErrorInvalidValue;
+        default: return hipErrorInvalidValue;  // mode 3 (normest's rescale) stays on CSR
+    }
 }
 
 template <int MODE>

@@ -205,11 +205,51 @@ static void free_matrix(cal_ctx* c) {
     if (A.rowkey8) hipFree(A.rowkey8);
     if (A.rowmask) hipFree(A.rowmask);
     if (A.wavemask) hipFree(A.wavemask);
+    if (A.ds_rowmask) hipFree(A.ds_rowmask);
+    if (A.ds_wavemask) hipFree(A.ds_wavemask);
+    if (A.ds_diag) hipFree(A.ds_diag);
+    if (A.ds_gsum) hipFree(A.ds_gsum);
+    if (A.ds_dprod) hipFree(A.ds_dprod);
     A = DevMatrix();
     if (c->d_work) hipFree(c->d_work);
     c->d_work = nullptr;
     c->work_cols = 0;
     c->has_A = false;
+}
+
+// the row-pattern tables of a matrix that goes on as a CSR matrix
+static void drop_patterns(DevMatrix& A) {
+    void** const ptrs[] = {(void**)&A.pat,    (void**)&A.pinfo,  (void**)&A.pdelta,  (void**)&A.pval,    (void**)&A.ppat,
+                           (void**)&A.ppinfo, (void**)&A.ppoff,  (void**)&A.ppval,   (void**)&A.rzval,   (void**)&A.rzmask,
+                           (void**)&A.rowkey8, (void**)&A.rowmask, (void**)&A.wavemask};
+    for (void** p : ptrs) {
+        if (*p) hipFree(*p);
+        *p = nullptr;
+    }
+    A.use_pat = A.use_pair = A.pcanon = A.cuniform = false;
+    A.npat = A.nent = A.maxlen = A.nppat = A.npent = A.pmaxlen = 0;
+    A.npsplit = 0;
+    A.plane_P = 0;
+    A.plane_H = 0;
+    for (int k = 0; k < 8; ++k) {
+        A.pslot[k] = 0;
+        A.cval[k] = 0.0;
+    }
+}
+
+// the diagonal-split tables of a matrix that goes on as a plain CSR matrix
+static void drop_dsplit(DevMatrix& A) {
+    void** const ptrs[] = {(void**)&A.ds_rowmask, (void**)&A.ds_wavemask, (void**)&A.ds_diag, (void**)&A.ds_gsum,
+                           (void**)&A.ds_dprod};
+    for (void** p : ptrs) {
+        if (*p) hipFree(*p);
+        *p = nullptr;
+    }
+    A.use_dsplit = false;
+    A.ds_L = 0;
+    A.ds_P = 0;
+    A.ds_H = 0;
+    A.ds_neg1 = false;
 }
 
 // ---- row-pattern analysis -------------------------------------------------
@@ -374,6 +414,163 @@ static bool build_pair_patterns(int64_t n, int64_t org, const std::vector<uint16
     return !ppinfo.empty();
 }
 
+// The plane march's host tables for a matrix in L canonical slots (k_spmv_planes,
+// k_resid_planes): the slots include -P and +P (the largest offset, P >= 256)
+// and the other slots reach H <= 256 rows: lap3d (P = N^2, H = N + 1) and
+// lap2d (P = N, H = 2) qualify.  False: no plane structure.  The caller
+// checks that the matrix is a whole single slab and bounds npat * L.
+struct PlaneTables {
+    std::vector<double> rz;          // npat x L slot values, +0.0 where the pattern has no entry
+    std::vector<uint8_t> rm;         // npat slot masks
+    bool uni = false;                // one value per slot over every pattern that has it
+    double cval[8] = {};             // those values
+    std::vector<uint8_t> rowmask;    // uni: the rows' slot masks + 8 zero bytes (dword key loads)
+    std::vector<uint32_t> wavemask;  // DevMatrix::wavemask
+    int64_t P = 0;
+    int H = 0;
+};
+
+static bool plane_analyze(int64_t n_rows, int L, const int* pslot, const std::vector<uint16_t>& pat,
+                          const std::vector<int2>& pinfo, const std::vector<int>& pdelta,
+                          const std::vector<double>& pval, PlaneTables& t) {
+    if (L < 2 || L > 8 || pslot[L - 1] < 256 || pslot[0] != -pslot[L - 1]) return false;
+    int H = 0;
+    for (int e = 1; e < L - 1; ++e) H = std::max(H, std::abs(pslot[e]));
+    H = (H + 1) & ~1;
+    if (H > 256) return false;
+    const int npat = (int)pinfo.size();
+    t.rz.assign((size_t)npat * L, 0.0);
+    t.rm.assign((size_t)npat, 0);
+    for (int q = 0; q < npat; ++q)
+        for (int e = 0; e < pinfo[q].y; ++e) {
+            const int o = pdelta[pinfo[q].x + e];
+            for (int k = 0; k < L; ++k)
+                if (pslot[k] == o) {
+                    t.rz[(size_t)q * L + k] = pval[pinfo[q].x + e];
+                    t.rm[q] |= (uint8_t)(1u << k);
+                }
+        }
+    // uniform slot values: one value per slot over every pattern that has it
+    bool uni = true;
+    for (int k = 0; k < L && uni; ++k) {
+        bool seen = false;
+        for (int q = 0; q < npat && uni; ++q)
+            if (t.rm[q] >> k & 1u) {
+                const double v = t.rz[(size_t)q * L + k];
+                if (!seen) t.cval[k] = v;
+                else uni = std::memcmp(&v, &t.cval[k], 8) == 0;
+                seen = true;
+            }
+    }
+    t.uni = uni;
+    if (uni) {
+        t.rowmask.assign((size_t)n_rows + 8, 0);
+        for (int64_t r = 0; r < n_rows; ++r) t.rowmask[(size_t)r] = t.rm[pat[(size_t)r]];
+    }
+    t.P = pslot[L - 1];
+    t.H = H;
+    // the waves' missing-slot masks (cal_internal.hpp DevMatrix::wavemask)
+    const int64_t P = t.P;
+    const int64_t nxy = (P + kPlaneBlockRows - 1) / kPlaneBlockRows;
+    const int64_t nz = (n_rows + P - 1) / P;
+    const unsigned full = (1u << L) - 1u;
+    t.wavemask.assign((size_t)(nz + 1) * nxy, 0u);
+    for (int64_t z = 0; z < nz; ++z)
+        for (int64_t b = 0; b < nxy; ++b) {
+            uint32_t v = 0;
+            for (int w = 0; w < 4; ++w) {
+                unsigned m = 0;
+                const int64_t r0 = z * P + b * kPlaneBlockRows + 128 * w;
+                for (int64_t r = r0; r < r0 + 128; ++r) m |= r < n_rows ? full & ~(unsigned)t.rm[pat[(size_t)r]] : full;
+                v |= (uint32_t)m << (8 * w);
+            }
+            t.wavemask[(size_t)(z * nxy + b)] = v;
+        }
+    return true;
+}
+
+// ---- the diagonal-split format ---------------------------------------------
+// H = K + diag(V): a uniform stencil K on the plane march and the diagonal as
+// one streamed vector (kernels.hip PlaneMarch DG).  The matrix
+// (n rows, a whole single slab; the caller checks that) qualifies when, with
+// every offset-0 value replaced by one placeholder, the analysis of the
+// row-pattern format above gives canonical slots on the plane march with
+// uniform slot values, within what the DG kernels are instantiated for: 5 or
+// 7 slots with the offsets -1, 0, +1 in the middle.  A row without a stored
+// diagonal entry keeps its mask bit clear and gets diag = +0.0.
+struct SplitPlan {
+    int L = 0;
+    int slot[8] = {};
+    double cval[8] = {};
+    int64_t P = 0;
+    int H = 0;
+    bool neg1 = false;
+    std::vector<uint8_t> rowmask;
+    std::vector<uint32_t> wavemask;
+    std::vector<double> diag;
+};
+
+static bool split_analyze(int64_t n, const std::vector<int>& rowptr, const std::vector<int>& col, const double* val,
+                          SplitPlan& sp) {
+    // the vectors' leading dimension (upload_matrix) must stay below 2^28 rows
+    if (n < 1 || ((n + 2 + 63) / 64) * 64 >= ((int64_t)1 << 28)) return false;
+    // cheap rejections before the pattern build: rows of at most 8 entries in
+    // strictly ascending column order, at most 8 distinct offsets
+    int off[8], noff = 0;
+    for (int64_t r = 0; r < n; ++r) {
+        const int p0 = rowptr[r], len = rowptr[r + 1] - p0;
+        if (len > 8) return false;
+        for (int j = 0; j < len; ++j) {
+            if (j > 0 && col[p0 + j] <= col[p0 + j - 1]) return false;
+            const int o = col[p0 + j] - (int)r;
+            int k = 0;
+            while (k < noff && off[k] != o) ++k;
+            if (k == noff) {
+                if (noff == 8) return false;
+                off[noff++] = o;
+            }
+        }
+    }
+    std::sort(off, off + noff);
+    const int L = noff, m = L / 2;
+    if ((L != 5 && L != 7) || off[m - 1] != -1 || off[m] != 0 || off[m + 1] != 1) return false;
+    if (off[L - 1] < 256 || off[0] != -off[L - 1]) return false;
+    // the values with one placeholder on the diagonal
+    const double placeholder = 1.0;
+    std::vector<double> v2(val, val + rowptr[n]);
+    sp.diag.assign((size_t)n + 2, 0.0);
+    for (int64_t r = 0; r < n; ++r)
+        for (int p = rowptr[r]; p < rowptr[r + 1]; ++p)
+            if (col[p] == (int)r) {
+                sp.diag[(size_t)r] = val[p];
+                v2[p] = placeholder;
+            }
+    std::vector<uint16_t> pat, ppat;
+    std::vector<int2> pinfo, ppinfo;
+    std::vector<int> pdelta, ppoff;
+    std::vector<double> pval, ppval;
+    int mx = 0, pmx = 0, slots[8] = {};
+    bool canon = false;
+    if (!build_patterns(n, 0, rowptr, col, v2.data(), pat, pinfo, pdelta, pval, &mx)) return false;
+    if (!build_pair_patterns(n, 0, pat, pinfo, pdelta, pval, col, ppat, ppinfo, ppoff, ppval, &pmx, &canon, slots))
+        return false;
+    if (!canon || pmx != L || (size_t)pinfo.size() * L > 2048) return false;
+    PlaneTables pt;
+    if (!plane_analyze(n, L, slots, pat, pinfo, pdelta, pval, pt) || !pt.uni) return false;
+    sp.L = L;
+    sp.neg1 = true;
+    for (int k = 0; k < L; ++k) {
+        sp.slot[k] = slots[k];
+        sp.cval[k] = pt.cval[k];
+        if (k != m && pt.cval[k] != -1.0) sp.neg1 = false;
+    }
+    sp.P = pt.P;
+    sp.H = pt.H;
+    sp.rowmask = std::move(pt.rowmask);
+    sp.wavemask = std::move(pt.wavemask);
+    return true;
+}
+
 // Upload a local matrix: n_rows stored rows, the n_local local ones from
 // stored row ext_off.  col: local column ids relative to the local origin
 // (negative ids address the left halo); lpad / rext: halo extent on either
@@ -399,7 +596,7 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
     A.ld = ((A.lpad + n_local + rext + 2 + 63) / 64) * 64;
     if (A.ld == 0) A.ld = 64;
     // storage format: row patterns when the table is small (auto) or forced
-    if (c->spmv_format != 1) {
+    if (c->spmv_format != 1 && c->spmv_format != 3) {
         std::vector<uint16_t> pat;
         std::vector<int2> pinfo;
         std::vector<int> pdelta;
@@ -443,87 +640,75 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
                 CAL_HIP(c, hipMemcpy(A.ppinfo, ppinfo.data(), ppinfo.size() * sizeof(int2), hipMemcpyHostToDevice));
                 CAL_HIP(c, hipMemcpy(A.ppoff, ppoff.data(), ppoff.size() * sizeof(int), hipMemcpyHostToDevice));
                 CAL_HIP(c, hipMemcpy(A.ppval, ppval.data(), ppval.size() * sizeof(double), hipMemcpyHostToDevice));
-                // the plane march (k_resid_planes): a single slab without halos whose
-                // canonical slots include -P and +P (the largest offset) and whose
-                // other slots reach H <= 256 rows: lap3d (P = N^2, H = N + 1) and
-                // lap2d (P = N, H = 2) qualify
-                const int L = A.pmaxlen;
-                if (A.pcanon && L >= 2 && ext_off == 0 && n_rows == n_local && A.lpad == 0 &&
-                    A.pslot[L - 1] >= 256 && A.pslot[0] == -A.pslot[L - 1] && (size_t)A.npat * L <= 2048) {
-                    int H = 0;
-                    for (int e = 1; e < L - 1; ++e) H = std::max(H, std::abs(A.pslot[e]));
-                    H = (H + 1) & ~1;
-                    if (H <= 256) {
-                        std::vector<double> rz((size_t)A.npat * L, 0.0);
-                        std::vector<uint8_t> rm((size_t)A.npat, 0);
-                        for (int q = 0; q < A.npat; ++q)
-                            for (int e = 0; e < pinfo[q].y; ++e) {
-                                const int o = pdelta[pinfo[q].x + e];
-                                for (int k = 0; k < L; ++k)
-                                    if (A.pslot[k] == o) {
-                                        rz[(size_t)q * L + k] = pval[pinfo[q].x + e];
-                                        rm[q] |= (uint8_t)(1u << k);
-                                    }
-                            }
-                        CAL_HIP(c, hipMalloc((void**)&A.rzval, rz.size() * sizeof(double)));
-                        CAL_HIP(c, hipMemcpy(A.rzval, rz.data(), rz.size() * sizeof(double), hipMemcpyHostToDevice));
-                        CAL_HIP(c, hipMalloc((void**)&A.rzmask, rm.size()));
-                        CAL_HIP(c, hipMemcpy(A.rzmask, rm.data(), rm.size(), hipMemcpyHostToDevice));
-                        // uniform slot values: one value per slot over every pattern that has it
-                        bool uni = true;
-                        for (int k = 0; k < L && uni; ++k) {
-                            bool seen = false;
-                            for (int q = 0; q < A.npat && uni; ++q)
-                                if (rm[q] >> k & 1u) {
-                                    const double v = rz[(size_t)q * L + k];
-                                    if (!seen) A.cval[k] = v;
-                                    else uni = std::memcmp(&v, &A.cval[k], 8) == 0;
-                                    seen = true;
-                                }
-                        }
-                        if (uni) {  // 1-B mask keys (8 zero bytes past the rows: dword key loads)
-                            std::vector<uint8_t> km((size_t)n_rows + 8, 0);
-                            for (int64_t r = 0; r < n_rows; ++r) km[(size_t)r] = rm[pat[(size_t)r]];
-                            CAL_HIP(c, hipMalloc((void**)&A.rowmask, km.size()));
-                            CAL_HIP(c, hipMemcpy(A.rowmask, km.data(), km.size(), hipMemcpyHostToDevice));
-                            A.cuniform = true;
-                        } else if (A.npat <= 256) {  // 1-B keys (8 zero bytes past the rows: dword key loads)
-                            std::vector<uint8_t> k8((size_t)n_rows + 8, 0);
-                            for (int64_t r = 0; r < n_rows; ++r) k8[(size_t)r] = (uint8_t)pat[(size_t)r];
-                            CAL_HIP(c, hipMalloc((void**)&A.rowkey8, k8.size()));
-                            CAL_HIP(c, hipMemcpy(A.rowkey8, k8.data(), k8.size(), hipMemcpyHostToDevice));
-                        }
-                        A.plane_P = A.pslot[L - 1];
-                        A.plane_H = H;
-                        // the waves' missing-slot masks (cal_internal.hpp DevMatrix::wavemask)
-                        {
-                            const int64_t P = A.plane_P;
-                            const int64_t nxy = (P + kPlaneBlockRows - 1) / kPlaneBlockRows;
-                            const int64_t nz = (n_rows + P - 1) / P;
-                            const unsigned full = (1u << L) - 1u;
-                            std::vector<uint32_t> wm((size_t)(nz + 1) * nxy, 0u);
-                            for (int64_t z = 0; z < nz; ++z)
-                                for (int64_t b = 0; b < nxy; ++b) {
-                                    uint32_t v = 0;
-                                    for (int w = 0; w < 4; ++w) {
-                                        unsigned m = 0;
-                                        const int64_t r0 = z * P + b * kPlaneBlockRows + 128 * w;
-                                        for (int64_t r = r0; r < r0 + 128; ++r)
-                                            m |= r < n_rows ? full & ~(unsigned)rm[pat[(size_t)r]] : full;
-                                        v |= (uint32_t)m << (8 * w);
-                                    }
-                                    wm[(size_t)(z * nxy + b)] = v;
-                                }
-                            CAL_HIP(c, hipMalloc((void**)&A.wavemask, wm.size() * sizeof(uint32_t)));
-                            CAL_HIP(c, hipMemcpy(A.wavemask, wm.data(), wm.size() * sizeof(uint32_t),
-                                                 hipMemcpyHostToDevice));
-                        }
+                // the plane march (plane_analyze): a single slab without halos
+                PlaneTables pt;
+                if (A.pcanon && ext_off == 0 && n_rows == n_local && A.lpad == 0 && (size_t)A.npat * A.pmaxlen <= 2048 &&
+                    plane_analyze(n_rows, A.pmaxlen, A.pslot, pat, pinfo, pdelta, pval, pt)) {
+                    CAL_HIP(c, hipMalloc((void**)&A.rzval, pt.rz.size() * sizeof(double)));
+                    CAL_HIP(c, hipMemcpy(A.rzval, pt.rz.data(), pt.rz.size() * sizeof(double), hipMemcpyHostToDevice));
+                    CAL_HIP(c, hipMalloc((void**)&A.rzmask, pt.rm.size()));
+                    CAL_HIP(c, hipMemcpy(A.rzmask, pt.rm.data(), pt.rm.size(), hipMemcpyHostToDevice));
+                    for (int k = 0; k < 8; ++k) A.cval[k] = pt.cval[k];
+                    if (pt.uni) {  // 1-B mask keys
+                        CAL_HIP(c, hipMalloc((void**)&A.rowmask, pt.rowmask.size()));
+                        CAL_HIP(c, hipMemcpy(A.rowmask, pt.rowmask.data(), pt.rowmask.size(), hipMemcpyHostToDevice));
+                        A.cuniform = true;
+                    } else if (A.npat <= 256) {  // 1-B keys (8 zero bytes past the rows: dword key loads)
+                        std::vector<uint8_t> k8((size_t)n_rows + 8, 0);
+                        for (int64_t r = 0; r < n_rows; ++r) k8[(size_t)r] = (uint8_t)pat[(size_t)r];
+                        CAL_HIP(c, hipMalloc((void**)&A.rowkey8, k8.size()));
+                        CAL_HIP(c, hipMemcpy(A.rowkey8, k8.data(), k8.size(), hipMemcpyHostToDevice));
                     }
+                    A.plane_P = pt.P;
+                    A.plane_H = pt.H;
+                    CAL_HIP(c, hipMalloc((void**)&A.wavemask, pt.wavemask.size() * sizeof(uint32_t)));
+                    CAL_HIP(c, hipMemcpy(A.wavemask, pt.wavemask.data(), pt.wavemask.size() * sizeof(uint32_t),
+                                         hipMemcpyHostToDevice));
                 }
             }
         } else if (c->spmv_format == 2) {
             return set_error(c, CAL_ERR_UNSUPPORTED, "row-pattern format requested but the matrix has too many "
                                                      "distinct rows (or rows longer than 32)");
+        }
+    }
+    // The diagonal-split format (split_analyze): forced ("split"), or under
+    // "auto" for a qualifying matrix that the analysis above left on CSR or on
+    // the row / pair kernels (plane_P == 0).  A matrix on the plane march keeps
+    // its path.  The matrix is then a CSR matrix (use_pat false) to everything
+    // but the SpMV dispatch: the row-pattern tables are dropped.
+    if (c->spmv_format == 3 || (c->spmv_format == 0 && (!A.use_pat || A.plane_P == 0))) {
+        const bool slab = ext_off == 0 && n_rows == n_local && n_local == n_global && A.lpad == 0 &&
+                          !(c->comm && c->comm->nranks > 1);
+        SplitPlan sp;
+        if (slab && split_analyze(n_rows, rowptr, col, val, sp)) {
+            drop_patterns(A);
+            CAL_HIP(c, hipMalloc((void**)&A.ds_rowmask, sp.rowmask.size()));
+            CAL_HIP(c, hipMemcpy(A.ds_rowmask, sp.rowmask.data(), sp.rowmask.size(), hipMemcpyHostToDevice));
+            CAL_HIP(c, hipMalloc((void**)&A.ds_wavemask, sp.wavemask.size() * sizeof(uint32_t)));
+            CAL_HIP(c, hipMemcpy(A.ds_wavemask, sp.wavemask.data(), sp.wavemask.size() * sizeof(uint32_t),
+                                 hipMemcpyHostToDevice));
+            CAL_HIP(c, hipMalloc((void**)&A.ds_diag, sp.diag.size() * sizeof(double)));
+            CAL_HIP(c, hipMemcpy(A.ds_diag, sp.diag.data(), sp.diag.size() * sizeof(double), hipMemcpyHostToDevice));
+            // mode 4's group sums and edge products (kernels.hip k_dsplit_dot)
+            const size_t ng = (size_t)n_rows / 64 + 2, np = (size_t)n_rows + 64;
+            CAL_HIP(c, hipMalloc((void**)&A.ds_gsum, ng * sizeof(double)));
+            CAL_HIP(c, hipMemset(A.ds_gsum, 0, ng * sizeof(double)));
+            CAL_HIP(c, hipMalloc((void**)&A.ds_dprod, np * sizeof(double)));
+            CAL_HIP(c, hipMemset(A.ds_dprod, 0, np * sizeof(double)));
+            A.ds_L = sp.L;
+            for (int k = 0; k < 8; ++k) {
+                A.ds_slot[k] = sp.slot[k];
+                A.ds_cval[k] = sp.cval[k];
+            }
+            A.ds_P = sp.P;
+            A.ds_H = sp.H;
+            A.ds_neg1 = sp.neg1;
+            A.use_dsplit = true;
+        } else if (c->spmv_format == 3) {
+            return set_error(c, CAL_ERR_UNSUPPORTED,
+                             "diagonal-split format requested but the matrix does not qualify: it needs a whole "
+                             "single slab, rows of at most 8 entries and a uniform 5- or 7-slot stencil -P .. -1, 0, "
+                             "+1 .. +P (P >= 256, in-plane reach <= 256) around a per-row diagonal");
         }
     }
     // CSR-stream row blocks over the local rows (the CSR path never runs on
@@ -533,6 +718,17 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
     std::vector<int> rp_loc(rowptr.begin() + ext_off, rowptr.begin() + ext_off + n_local + 1);
     build_row_blocks(n_local, rp_loc, blk, &max_nnz);
     A.nblk = (int)blk.size() - 1;
+    // the split format's fused Lanczos dot sums in the CSR kernel's order, which
+    // it takes to be 256 consecutive rows per block (rows of at most 8 entries)
+    // -- a guard, not a case that occurs.  "auto" then goes on with CSR.
+    if (A.use_dsplit)
+        for (size_t i = 0; i < blk.size(); ++i)
+            if (blk[i] != (int)std::min<int64_t>(256 * (int64_t)i, n_local)) {
+                drop_dsplit(A);
+                if (c->spmv_format == 3)
+                    return set_error(c, CAL_ERR_UNSUPPORTED, "diagonal-split format: unexpected CSR row blocks");
+                break;
+            }
     int nit = (max_nnz + 255) / 256;
     if (nit < 1) nit = 1;
     if (nit > 8) nit = 8;
@@ -551,6 +747,43 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
     c->A_gen++;
     return 0;
 }
+
+// the launch description of the diagonal-split SpMV over the whole slab
+static PatArgs dsplit_args(const DevMatrix& A, const double* x, double* y, int mode, double shift, double im2,
+                           const double* xprev) {
+    PatArgs p{};
+    p.n = A.n_local;
+    p.nblk = (int)((A.n_local + 255) / 256);
+    p.x = x;
+    p.y = y;
+    p.xprev = xprev;
+    p.shift = shift;
+    p.im2 = im2;
+    p.mode = mode;
+    p.pmaxlen = A.ds_L;
+    p.pcanon = 1;
+    p.pmid = A.ds_L / 2;
+    for (int k = 0; k < 8; ++k) {
+        p.pslot[k] = A.ds_slot[k];
+        p.cval[k] = A.ds_cval[k];
+    }
+    p.xlo = 0;
+    p.xhi = A.ld;
+    p.ld = A.ld;
+    p.rowmask = A.ds_rowmask;
+    p.wavemask = A.ds_wavemask;
+    p.cuniform = 1;
+    p.plane_P = A.ds_P;
+    p.plane_H = A.ds_H;
+    p.diag = A.ds_diag;
+    p.gsum = A.ds_gsum;
+    p.dprod = A.ds_dprod;
+    return p;
+}
+
+// algorithmic bytes of a diagonal-split SpMV: the mask key, the diagonal, x
+// and y per row, and the previous power / Lanczos vector when there is one
+static double dsplit_spmv_bytes(int64_t len, bool prev) { return (double)len * (1 + 8 + 16 + (prev ? 8 : 0)); }
 
 static PatArgs pat_args(const DevMatrix& A, int64_t o, int64_t len, const double* x, double* y, int mode,
                         double shift, double im2, const double* xprev) {
@@ -635,6 +868,7 @@ hipError_t spmv_on_stream(const cal_ctx* c, const double* x, double* y, int mode
         if (mode != 0) return hipErrorInvalidValue;
         return launch_spmv_pat(pat_args(A, A.ext_off, A.n_local, x, y, 0, 0.0, 0.0, nullptr), st);
     }
+    if (A.use_dsplit && mode == 0) return launch_spmv_dsplit(dsplit_args(A, x, y, 0, 0.0, 0.0, nullptr), st);
     SpmvArgs a;
     a.rowptr = A.rowptr;
     a.col = A.col;
@@ -715,6 +949,14 @@ int spmv_dev(cal_ctx* c, const double* x, double* y, int mode, double shift, dou
     if (mode == 3 && (c->A.use_pat || !xnrm)) return set_error(c, CAL_ERR_ARG, "spmv_dev: mode 3 needs CSR and xnrm");
     CAL_TRY(halo_exchange(c, const_cast<double*>(x)));
     if (c->A.use_pat) return spmv_range(c, c->A.ext_off, c->A.n_local, x, y, mode, shift, im2, xprev);
+    if (c->A.use_dsplit && mode != 3) {
+        if (mode < 0 || mode > 2 || (mode == 2 && !xprev)) return set_error(c, CAL_ERR_ARG, "spmv_dev: bad mode");
+        c->stat_spmv_rows += c->A.n_local;
+        const int t = timer_begin(c, 0, dsplit_spmv_bytes(c->A.n_local, mode == 2));
+        CAL_HIP(c, launch_spmv_dsplit(dsplit_args(c->A, x, y, mode, shift, im2, mode == 2 ? xprev : nullptr), c->stream));
+        timer_end(c, t);
+        return 0;
+    }
     SpmvArgs a;
     a.xnrm = xnrm;
     a.rowptr = c->A.rowptr;
@@ -762,6 +1004,7 @@ static SpmvArgs csr_args(const cal_ctx* c, const double* x, double* y, int mode)
 int spmv_lanczos_parts(const cal_ctx* c, const double* x, const double* xprev, double* y) {
     const DevMatrix& A = c->A;
     if (!c->has_A || (c->comm && c->comm->nranks > 1)) return 0;
+    if (A.use_dsplit) return spmv_dsplit_blocks(dsplit_args(A, x, y, 4, 0.0, 0.0, xprev));
     if (!A.use_pat) return spmv_lanczos_blocks(csr_args(c, x, y, 4));
     return spmv_pat_lanczos_blocks(pat_args(A, A.ext_off, A.n_local, x, y, 4, 0.0, 0.0, xprev));
 }
@@ -779,6 +1022,15 @@ int spmv_lanczos_dev(cal_ctx* c, const double* x, const double* xprev, const dou
         p.dotp = dotp;
         const int t = timer_begin(c, 0, pat_spmv_bytes(A, A.n_local, has ? 2 : 0));
         CAL_HIP(c, launch_spmv_pat(p, c->stream));
+        timer_end(c, t);
+        return 0;
+    }
+    if (A.use_dsplit) {
+        PatArgs p = dsplit_args(A, x, y, 4, 0.0, 0.0, has ? xprev : nullptr);
+        p.pb2 = has ? pb2 : nullptr;
+        p.dotp = dotp;
+        const int t = timer_begin(c, 0, dsplit_spmv_bytes(A.n_local, has));
+        CAL_HIP(c, launch_spmv_dsplit(p, c->stream));
         timer_end(c, t);
         return 0;
     }
@@ -1130,7 +1382,8 @@ int cal_set_spmv_format(cal_ctx* c, const char* fmt) {
     if (!strcmp(fmt, "auto")) c->spmv_format = 0;
     else if (!strcmp(fmt, "csr")) c->spmv_format = 1;
     else if (!strcmp(fmt, "pattern")) c->spmv_format = 2;
-    else return set_error(c, CAL_ERR_ARG, "spmv format must be auto, csr or pattern");
+    else if (!strcmp(fmt, "split")) c->spmv_format = 3;
+    else return set_error(c, CAL_ERR_ARG, "spmv format must be auto, csr, pattern or split");
     return 0;
 }
 
@@ -1159,6 +1412,42 @@ int cal_spmv_plane_info(cal_ctx* c, int64_t* plane_P, int* plane_H, int* key_mod
     if (plane_H) *plane_H = on ? c->A.plane_H : 0;
     if (key_mode) *key_mode = !on ? -1 : (c->A.cuniform ? 0 : (c->A.npat <= 256 ? 1 : 2));
     return 0;
+}
+
+int cal_spmv_split_info(cal_ctx* c, int* on, int64_t* P, int* H, int* neg1) {
+    if (!c) return CAL_ERR_ARG;
+    if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    const bool s = c->A.use_dsplit;
+    if (on) *on = s ? 1 : 0;
+    if (P) *P = s ? c->A.ds_P : 0;
+    if (H) *H = s ? c->A.ds_H : 0;
+    if (neg1) *neg1 = s && c->A.ds_neg1 ? 1 : 0;
+    return 0;
+}
+
+// host only (calanczos_host.h): the upload's own analysis, no device call
+int cal_split_analyze(int64_t n, const int64_t* rowptr, const int32_t* colind, const double* val, int64_t* P, int* H,
+                      int* neg1) {
+    if (P) *P = 0;
+    if (H) *H = 0;
+    if (neg1) *neg1 = 0;
+    if (n < 1 || n >= ((int64_t)1 << 31) || !rowptr || rowptr[0] != 0) return 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (rowptr[i + 1] < rowptr[i]) return 0;
+    const int64_t nnz = rowptr[n];
+    if (nnz >= ((int64_t)1 << 31) || (nnz > 0 && (!colind || !val))) return 0;
+    std::vector<int> rp(n + 1), col(nnz);
+    for (int64_t i = 0; i <= n; ++i) rp[i] = (int)rowptr[i];
+    for (int64_t p = 0; p < nnz; ++p) {
+        if (colind[p] < 0 || colind[p] >= n) return 0;
+        col[p] = colind[p];
+    }
+    cal::SplitPlan sp;
+    if (!cal::split_analyze(n, rp, col, val, sp)) return 0;
+    if (P) *P = sp.P;
+    if (H) *H = sp.H;
+    if (neg1) *neg1 = sp.neg1 ? 1 : 0;
+    return 1;
 }
 
 int cal_spmv_format(cal_ctx* c, int* is_pattern, int* npatterns, int* nentries) {

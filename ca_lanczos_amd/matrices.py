@@ -73,6 +73,27 @@ def laplacian_3d(N: int) -> sp.csr_matrix:
     return sp.csr_matrix((val, col, rowptr), shape=(N ** 3, N ** 3))
 
 
+def grid_hamiltonian(dims, V, h: float = 1.0, mass: float = 1.0) -> sp.csr_matrix:
+    """``H = 1/(2 m h^2) * L + diag(V)`` on a 2-D or 3-D grid ``dims`` (first
+    dimension fastest), L the Dirichlet Laplacian (stencil 2d, -1) and V the
+    potential, one value per grid point: the grid Hamiltonian K + V of a
+    particle of mass ``mass`` on a mesh of width ``h`` (CSR, sorted int32
+    columns).  The off-diagonals are the uniform -1/(2 m h^2); the diagonal
+    d/(m h^2) + V differs from row to row (``spmv_format="split"``)."""
+    dims = tuple(int(d) for d in dims)
+    if len(dims) not in (2, 3):
+        raise ValueError("grid_hamiltonian: dims must be 2-D or 3-D")
+    n = int(np.prod(dims))
+    V = np.asarray(V, dtype=np.float64).ravel()
+    if V.shape[0] != n:
+        raise ValueError("grid_hamiltonian: V must have one value per grid point (%d)" % n)
+    t = 1.0 / (2.0 * float(mass) * float(h) * float(h))
+    rowptr, col, val = _stencil_csr(dims, 2.0 * len(dims))
+    val *= t
+    val[col == np.repeat(np.arange(n, dtype=col.dtype), np.diff(rowptr))] += V
+    return sp.csr_matrix((val, col, rowptr), shape=(n, n))
+
+
 def laplacian_rows(dim: int, N: int, r0: int, r1: int):
     """Rows [r0, r1) of the 2-D/3-D Laplacian with global int64 columns (a
     row slab of the distributed config 4): (rowptr, col, val)."""

@@ -107,9 +107,22 @@ int cal_mpk_schedule(cal_ctx* ctx, int* schedule);
 int cal_powers_launches(cal_ctx* ctx, int* launches);
 /* Device storage of A, chosen at the next cal_set_matrix_*: "auto" (default:
  * row patterns when A has <= 65535 distinct rows of <= 32 entries, else
- * CSR), "csr", or "pattern".  Both are lossless and give bit-identical SpMV
- * results (same per-row summation order). */
+ * CSR), "csr", "pattern" or "split".  All are lossless and give bit-identical
+ * SpMV results (same per-row summation order).
+ * "split" forces the diagonal-split format for grid Hamiltonians H = K +
+ * diag(V): a uniform 5- or 7-slot stencil K (offsets -P .. -1, 0, +1 .. +P, P
+ * >= 256, in-plane reach <= 256, rows of at most 8 entries, a whole single
+ * slab) on the plane-march kernel and the per-row diagonal as one streamed
+ * vector; cal_set_matrix_* returns CAL_ERR_UNSUPPORTED for a matrix that does
+ * not qualify.  "auto" takes it for a qualifying matrix that would otherwise
+ * run on CSR or on the row / pair kernels; "csr" never does.  Everything but
+ * the SpMV (residuals, normest's rescale) runs on the matrix's CSR copy, and
+ * cal_spmv_format keeps reporting CSR for it. */
 int cal_set_spmv_format(cal_ctx* ctx, const char* fmt);
+/* The diagonal-split format of the resident matrix: *on = 1 when its SpMV
+ * runs there, with the plane stride P, the in-plane reach H and *neg1 = 1
+ * when every off-diagonal is -1; zeros otherwise. */
+int cal_spmv_split_info(cal_ctx* ctx, int* on, int64_t* P, int* H, int* neg1);
 int cal_spmv_format(cal_ctx* ctx, int* is_pattern, int* npatterns, int* nentries);
 /* Pair patterns of the row-pattern format (two rows per lane): number of
  * merged pair patterns, their table entries, and pairs on the per-row path. */

@@ -54,6 +54,15 @@ int cal_qrstep(int m, double* H, int ldh, double* W, int ldw, double mu);
  * for a non-finite T. */
 int cal_expm_col1(int m, const double* T, int ldt, double dt, double* c_re, double* c_im);
 
+/* Whether a CSR matrix (n rows, int64 row pointers, int32 sorted columns)
+ * qualifies for the diagonal-split SpMV format (cal_set_spmv_format "split"):
+ * 1 with the plane stride *P, the in-plane reach *H and *neg1 (every
+ * off-diagonal is -1), else 0 with zeros.  The analysis the upload itself
+ * runs, on the host alone; the slab conditions (one rank, the whole matrix)
+ * are the caller's. */
+int cal_split_analyze(int64_t n, const int64_t* rowptr, const int32_t* colind, const double* val, int64_t* P, int* H,
+                      int* neg1);
+
 /* Residency generation of the MEX shims' device copies of A (mex/
  * cal_mex_common.h).  Every shim keeps A resident across calls and re-uploads
  * it when the pointers, nnz, a sampled digest of jc/ir/pr or this

@@ -1,0 +1,214 @@
+#!/usr/bin/env python
+"""The diagonal-split SpMV format on a grid Hamiltonian K + diag(V), against
+the same matrix on CSR and against the plain Laplacian's plane march.
+
+  python tools/hamiltonian_bench.py [--N 215] [--rounds 2] [--windows 5]
+                                    [--only spmv,ca,lanczos,prop]
+                                    [--library NAME] [--out profiles/dsplit/NAME.json]
+
+Matrix: grid_hamiltonian((N, N, N), V) with the harmonic potential V = 0.5 w^2
+|x - x0|^2 (w = 0.02: V of the size of the kinetic term), h = mass = 1, so the
+off-diagonals are -1/2 (the general uniform-value kernel, not NEG1).  Variants,
+each in a fresh child process, alternating, --rounds times each:
+  split  Context(spmv_format="split")
+  csr    Context(spmv_format="csr")         the A/B partner
+  lap    laplacian_3d(N), format "auto"     the plane march, the yardstick
+A child measures, in --windows (>= 5) windows each after a warm-up:
+  spmv     mode 0 back to back, 50 launches per window, each bracketed by the
+           library's device events (cal_bench_spmv): mean us per launch;
+  ca       the CA loop (s = 8, Newton, 'local'), 10 outer iterations per
+           window, host clock around synchronised windows as bench.py;
+  lanczos  fused standard Lanczos, keep_Q = 0, 100 steps per window, as
+           tools/lanczos_bench.py;
+  prop     the propagator on blkdiag(H, H), s = 8, 3 blocks, 4 time steps per
+           window, as tools/prop_bench.py.
+The summary has median, min and max over all windows of a variant and, for
+split against csr, whether split is faster beyond the spread of both (split's
+slowest window under csr's fastest).  --library runs the children on another
+build of the library (CAL_LIBRARY), e.g. a kernel variant.  Prints one JSON
+line; --out also writes it to a file.  Needs a GPU.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+S, BLOCKS = 8, 3
+SPMV_PER_WINDOW, CA_PER_WINDOW, LZ_PER_WINDOW, PROP_PER_WINDOW = 50, 10, 100, 4
+
+
+def build(cal, np, variant, N):
+    if variant == "lap":
+        return cal.matrices.laplacian_3d(N)
+    idx = np.arange(N ** 3, dtype=np.int64)
+    r2 = np.zeros(N ** 3)
+    for d in range(3):
+        x = (idx // N ** d) % N - 0.5 * (N - 1)
+        r2 += x * x
+    return cal.matrices.grid_hamiltonian((N, N, N), 0.5 * 0.02 ** 2 * r2)
+
+
+def child(a):
+    import numpy as np
+
+    import ca_lanczos_amd as cal
+    from ca_lanczos_amd import _lib
+
+    N, W = a.N, a.windows
+    A = build(cal, np, a.variant, N)
+    n = A.shape[0]
+    fmt = {"split": "split", "csr": "csr", "lap": "auto"}[a.variant]
+    ctx = cal.Context(spmv_format=fmt).set_matrix(A)
+    out = dict(variant=a.variant, library=os.path.basename(_lib.LIB_PATH), n=n, nnz=int(A.nnz),
+               spmv_format=ctx.spmv_format(), plane_info=ctx.spmv_plane_info(), split_info=ctx.spmv_split_info())
+    only = a.only.split(",")
+    if "spmv" in only:
+        ctx.bench_spmv(20)
+        out["spmv_us"] = [1e3 * ctx.bench_spmv(SPMV_PER_WINDOW)[0] for _ in range(W)]
+        out["spmv_launches"] = W * SPMV_PER_WINDOW
+    r = np.random.default_rng(0).standard_normal(n)
+    if "ca" in only:
+        wu = 3
+        ctx.lanczos_begin(r, S, wu + W * CA_PER_WINDOW + 1, "newton", "local")
+        for _ in range(wu):
+            ctx.lanczos_step(False)
+        ctx.synchronize()
+        ms = []
+        for _ in range(W):
+            t0 = time.perf_counter()
+            for _ in range(CA_PER_WINDOW):
+                ctx.lanczos_step(False)
+            ctx.synchronize()
+            ms.append(1e3 * (time.perf_counter() - t0) / CA_PER_WINDOW)
+        info = ctx.lanczos_get()[4]
+        ctx.lanczos_end()
+        out["ca_ms_per_outer"] = ms
+        out["ca_flags"] = dict(n_reorth=info.n_reorth, breakdown=info.breakdown, n_rank_deficient=info.n_rank_deficient)
+    if "lanczos" in only:
+        wu = 50
+        ctx.std_lanczos_begin(r, wu + W * LZ_PER_WINDOW, "local", keep_Q=False)
+        ctx.std_lanczos_step(wu)
+        ctx.synchronize()
+        ms = []
+        for _ in range(W):
+            t0 = time.perf_counter()
+            ctx.std_lanczos_step(LZ_PER_WINDOW)
+            ctx.synchronize()
+            ms.append(1e3 * (time.perf_counter() - t0) / LZ_PER_WINDOW)
+        info = ctx.std_lanczos_get()[4]
+        ctx.std_lanczos_end()
+        out["lanczos_ms_per_vector"] = ms
+        out["lanczos_fused"] = info["fused"]
+    ctx.close()
+    if "prop" in only:
+        idx = np.arange(n)
+        coords = [(idx // N ** d) % N for d in range(3)]
+        r2 = sum((c - 0.5 * (N - 1)) ** 2 for c in coords)
+        phase = sum(k * c for k, c in zip((0.7, 0.3, 0.2), coords))
+        psi0 = np.exp(-r2 / (2 * (N / 8.0) ** 2)) * np.exp(1j * phase)
+        del idx, coords, r2, phase
+        ctx = cal.Context(spmv_format=fmt)
+        P = cal.Propagator(A, psi0, S, BLOCKS, basis="newton", ctx=ctx)
+        out["stacked_split_info"] = ctx.spmv_split_info()
+        out["stacked_plane_info"] = ctx.spmv_plane_info()
+        P.step(a.dt, 2)
+        ctx.synchronize()
+        ms = []
+        for _ in range(W):
+            t0 = time.perf_counter()
+            P.step(a.dt, PROP_PER_WINDOW)
+            ctx.synchronize()
+            ms.append(1e3 * (time.perf_counter() - t0) / PROP_PER_WINDOW)
+        info = P.info()
+        out["prop_ms_per_step"] = ms
+        out["prop_lsteps"] = info["lsteps"]
+        out["prop_residual_max"] = info["residual_max"]
+        P.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
+def run_child(a, variant):
+    env = dict(os.environ)
+    env.pop("CAL_LIBRARY", None)
+    env.pop("CAL_SPMV_FORMAT", None)
+    if a.library:
+        env["CAL_LIBRARY"] = a.library
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--variant", variant, "--N", str(a.N),
+           "--windows", str(a.windows), "--only", a.only, "--dt", str(a.dt)]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
+    if p.returncode != 0:
+        raise RuntimeError("child %s failed (%d): %s" % (variant, p.returncode, p.stderr[-2000:]))
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--N", type=int, default=215)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--only", default="spmv,ca,lanczos,prop")
+    ap.add_argument("--variants", default="split,csr,lap")
+    ap.add_argument("--dt", type=float, default=0.05)
+    ap.add_argument("--library", default=None)
+    ap.add_argument("--child-timeout", type=int, default=500)
+    ap.add_argument("--variant", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.windows < 5:
+        ap.error("--windows must be at least 5")
+    if a.child:
+        return child(a)
+
+    variants = a.variants.split(",")
+    res = dict(N=a.N, n=a.N ** 3, rounds=a.rounds, windows=a.windows, only=a.only, library=a.library or "production",
+               s=S, blocks=BLOCKS, runs={v: [] for v in variants})
+    for i in range(a.rounds):  # alternating, each in a fresh process
+        for v in variants:
+            res["runs"][v].append(run_child(a, v))
+            print("round %d: %s done" % (i + 1, v), file=sys.stderr, flush=True)
+
+    keys = dict(spmv="spmv_us", ca="ca_ms_per_outer", lanczos="lanczos_ms_per_vector", prop="prop_ms_per_step")
+    summ = {}
+    for v in variants:
+        summ[v] = {}
+        for k, field in keys.items():
+            w = [x for r in res["runs"][v] for x in r.get(field, [])]
+            if w:
+                med = statistics.median(w)
+                summ[v][k] = dict(median=med, min=min(w), max=max(w), windows=len(w), per_s=1e3 / med if k != "spmv" else None)
+    res["summary"] = summ
+    n = a.N ** 3
+    for v in variants:
+        if "spmv" in summ[v]:
+            per_row = 33.0 if v == "split" else 25.0  # algorithmic bytes per row of the marches
+            nnz = res["runs"][v][0]["nnz"]
+            b = per_row * n if v != "csr" else 12.0 * nnz + 20.0 * n
+            summ[v]["spmv"]["algorithmic_TBps"] = b / (summ[v]["spmv"]["median"] * 1e-6) / 1e12
+    if "split" in summ and "csr" in summ:
+        res["split_vs_csr"] = {
+            k: dict(ratio=summ["csr"][k]["median"] / summ["split"][k]["median"],
+                    beyond_spread=bool(summ["split"][k]["max"] < summ["csr"][k]["min"]))
+            for k in summ["split"] if k in summ["csr"]}
+    if "split" in summ and "lap" in summ:
+        res["split_over_lap_time"] = {k: summ["split"][k]["median"] / summ["lap"][k]["median"]
+                                      for k in summ["split"] if k in summ["lap"]}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
