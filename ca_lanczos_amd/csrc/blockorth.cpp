@@ -435,6 +435,47 @@ static bool orth_device_ok(cal_ctx* c, const Panel& Qp, const Panel& X) {
            rowapply_ok(w + m, m, true, w);
 }
 
+// The load policy of the block's three sweeps (k_rowapply RES, kernels.hip).
+// At the bench size the 17 columns (1.35 GB) stream through the 256 MiB
+// Infinity Cache three times, and the matrix powers written last -- still in
+// the cache when P1 starts -- are pushed out by the sweeps' own traffic
+// before most of them are read again.  With every other column loaded
+// non-temporally the last R columns of X stay resident through P1, pass A and
+// pass B.  Measured in the in-loop emulation (tools/residency_probe.hip,
+// profiles/residency/probe.json, n = 215^3, columns of 79.5 MB): step
+// 1163-1167 us with plain loads, 1102-1112 with R = 0, 1062-1069 with R = 3
+// (each R better than the one below it; 3 columns = 0.89 of the cache is the
+// most that was measured, 4 do not fit).
+//  * off (-1) when the sweep's columns fit the cache (config 2, the IRL, the
+//    multi-rank slabs), for any shape but w = 9, m = 8, and for 'full', whose
+//    pass B is k_passb_wide;
+//  * off unless X is the V block the powers have just written
+//    (lanczos_step's k >= 2 block): nothing else is known to be in the cache;
+//  * otherwise R = min(m, kSweepResMax, floor(budget / (8 n))).
+constexpr int kSweepResMax = 3;
+constexpr int64_t kSweepResBudget = ((int64_t)256 << 20) / 32 * 29;  // 0.906 of the cache
+static int sweep_policy(cal_ctx* c, int64_t n, int w, int m) {
+    int res = -1;
+    if (w == 9 && m == 8 && !c->pbw.want && !test_switch("CAL_TEST_SWEEP_STREAM_OFF")) {
+        const int64_t r = std::min<int64_t>(std::min(m, kSweepResMax), kSweepResBudget / (8 * std::max<int64_t>(n, 1)));
+        const bool large = (int64_t)n * 8 * (w + m) > ((int64_t)256 << 20);
+        // (the test build's switch applies the policy at any n, to any X)
+        if ((large && c->sweep_x_fresh) || test_switch("CAL_TEST_SWEEP_STREAM_ON")) res = (int)r;
+    }
+#ifdef CAL_TEST_HOOKS
+    c->test_sweep_res = res;
+#endif
+    return res;
+}
+
+#ifdef CAL_TEST_HOOKS  // the test build only (csrc/Makefile libcalanczos_testhooks.so)
+}  // namespace cal
+// The load policy the last device block orthogonalisation ran with (-1 off,
+// 0..3 resident columns; -2: none has run).
+extern "C" int cal_test_sweep_policy(cal_ctx* c) { return c ? c->test_sweep_res : -2; }
+namespace cal {
+#endif
+
 // Spin on the published sequence word.  No HIP call in the fast path: a
 // stream query would enqueue a marker behind the prefetched matrix powers and
 // stall the next dispatch.  After 2 s without the word, synchronise the stream
@@ -460,6 +501,7 @@ static int orth_device(cal_ctx* c, int64_t n, const Panel& Qp, const Panel& X, b
     const int w = Qp.total, m = X.total, nq = w < 8 ? w : 8, wp = w + m;
     const int WP = rowapply_wpmax(wp), MO = rowapply_mout(m);
     const Panel W = panel_concat(Qp, X);
+    const int res = sweep_policy(c, n, w, m);
     CAL_TRY(ensure_red(c, 4096));
     double* d_tile = c->d_red;
     double* d_st = c->d_red + 1024;
@@ -492,7 +534,7 @@ static int orth_device(cal_ctx* c, int64_t n, const Panel& Qp, const Panel& X, b
         for (int cc = 0; cc < 16; ++cc) ct.p[cc] = panel_slice(T, cc < nt ? cc : nt - 1, 1).ptr[0];
         ct.p[16] = w == 9 ? panel_slice(Qp, 8, 1).ptr[0] : ct.p[0];
         const int t = timer_begin(c, 1, 8.0 * n * (nt + (w == 9 ? 1 : 0)));
-        CAL_HIP(c, launch_rowgram(ct, nt, w == 9, n, (int)blocks, c->d_partial, c->stream));
+        CAL_HIP(c, launch_rowgram(ct, nt, w == 9, n, (int)blocks, c->d_partial, c->stream, res));
         timer_end(c, t);
     }
     CAL_TRY(ensure_pub(c));
@@ -518,7 +560,8 @@ static int orth_device(cal_ctx* c, int64_t n, const Panel& Qp, const Panel& X, b
     // pass A: Grams of Q1 = W M1, nothing stored
     {
         const int t = timer_begin(c, 1, 8.0 * n * wp);
-        CAL_HIP(c, launch_rowapply(cw, d_mbuf, wp, m, ol, 2, w, n, (int)blocks, c->d_partial, c->stream));
+        CAL_HIP(c, launch_rowapply(cw, d_mbuf, wp, m, ol, 2, w, n, (int)blocks, c->d_partial, c->stream, nullptr,
+                                   res));
         timer_end(c, t);
     }
     CAL_TRY(coef(1, 0));
@@ -557,7 +600,7 @@ static int orth_device(cal_ctx* c, int64_t n, const Panel& Qp, const Panel& X, b
     } else {
         const int t = timer_begin(c, 2, 8.0 * n * (wp + m));
         CAL_HIP(c, launch_rowapply(cw, d_mbuf, wp, m, ol, 3, w, n, (int)((n + 255) / 256), c->d_partial, c->stream,
-                                   gate));
+                                   gate, res));
         timer_end(c, t);
     }
     if (c->pre_wait) {  // e.g. the next step's matrix powers (lanczos_step)

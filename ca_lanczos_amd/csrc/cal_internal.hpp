@@ -323,8 +323,11 @@ struct OutList {
 };
 // kind: 0 store, 1 store + Gram, 2 Gram only (pass A), 3 chained store (pass B).
 // gate (kind 3): device flags; a nonzero gate[0] or gate[1] skips the store.
+// res: the sweep's load policy (kernels.hip k_rowapply RES; -1 = plain loads),
+// honoured by pass A and pass B of the 17 -> 8 block step.
 hipError_t launch_rowapply(const ColList& P, const double* dM, int wp, int m, const OutList& Y, int kind, int wq,
-                           int64_t n, int blocks, double* partial, hipStream_t st, const double* gate = nullptr);
+                           int64_t n, int blocks, double* partial, hipStream_t st, const double* gate = nullptr,
+                           int res = -1);
 // s x s coefficients of the two-sweep block orthogonalisation (phase 0 after
 // the P1 Gram, phase 1 after pass A); see kernels.hip k_orth_coef.
 // Phase 1 with hout != nullptr also publishes out (R, RY, flags; 516
@@ -340,7 +343,7 @@ hipError_t launch_orth_coef(int phase, const double* tile, double* st, double* m
 #endif
 constexpr int kRowGramBlocks = CAL_ROWGRAM_BLOCKS;
 hipError_t launch_rowgram(const ColList& P, int nt, bool has_extra, int64_t n, int blocks, double* partial,
-                          hipStream_t st);
+                          hipStream_t st, int res = -1);
 // pass B (w = 9, m = 8) fused with G = [Qp | Q_new | Qold]' Q_new (kernels.hip
 // k_passb_wide): passb_wide_tiles(wold) 16-column groups, at most
 // kPassbWideMaxTiles; partial entries j (16 tiles) + a, j < 8
@@ -585,6 +588,10 @@ struct cal_ctx {
         hipEvent_t ev = nullptr;
     } pbw;
     bool orth_redone = false;  // the last block was redone on the host path
+    // set by lanczos_step around its k >= 2 block: X is the trailing s columns
+    // of the V buffer the matrix powers have just written (blockorth.cpp
+    // sweep_policy)
+    bool sweep_x_fresh = false;
     hipEvent_t orth_event = nullptr;
     // device-coefficient block orthogonalisation: the pinned host-mapped
     // result page the phase-1 kernel publishes R / RY / flags into (h_pub,
@@ -625,6 +632,10 @@ struct cal_ctx {
     // the test build only (CAL_TEST_HOOKS): R of ca_lanczos's first block
     // (normalize, ca_lanczos.m:176), read back by cal_test_first_block_R
     std::vector<double> test_R1;
+    // the test build only: the load policy of the last device block
+    // orthogonalisation (blockorth.cpp sweep_policy), read back by
+    // cal_test_sweep_policy; -2 before the first one
+    int test_sweep_res = -2;
 };
 
 // ---- helpers shared by the host-side translation units -----------------

@@ -3309,12 +3309,33 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// RES (the load policy of a sweep too large for the Infinity Cache, chosen by
+// blockorth.cpp sweep_policy): -1 plain loads; 0..3: every column is loaded
+// non-temporally except the last RES columns of X (the panel's columns
+// XEND - RES .. XEND - 1; XEND = WPMAX, or 16 in the Gram-only form, whose
+// column 16 is Qp's extra column), the matrix powers written last, which
+// then stay in the cache from sweep to sweep.  A load's policy changes no
+// bits.
+template <int RES, int XEND, int C>
+__device__ __forceinline__ double sweep_load(const double* p) {
+    if constexpr (RES >= 0 && !(C >= XEND - RES && C < XEND)) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+template <int WPMAX, int RES, int XEND, int C = 0>
+__device__ __forceinline__ void sweep_load_row(const double* const* pc, int64_t rr, double* dst) {
+    if constexpr (C < WPMAX) {
+        dst[C] = sweep_load<RES, XEND, C>(pc[C] + rr);
+        sweep_load_row<WPMAX, RES, XEND, C + 1>(pc, rr, dst);
+    }
+}
+
 // gate (CHAIN only, may be null): the coefficient step's two failure flags
 // (k_orth_coef out[512..513]); when either is set the sweep stores nothing.
 // A failed Cholesky leaves M1 or M2 unwritten (stale scratch) and the host
 // redoes the block from its input -- which, in ca_lanczos's first block, is
 // the same storage as the output (q = Q(:,1)).
-template <int WPMAX, int MOUT, bool GRAM, bool APPLY = true, bool STORE = true, bool CHAIN = false, bool NTS = false>
+template <int WPMAX, int MOUT, bool GRAM, bool APPLY = true, bool STORE = true, bool CHAIN = false, bool NTS = false,
+          int RES = -1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_rowapply(ColList P, const double* __restrict__ M, int wp, int m,
                                                   OutList Y, int wq, int64_t n, double* __restrict__ partial,
                                                   const double* __restrict__ gate) {
@@ -3354,8 +3375,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     auto load_rows = [&](int64_t b, double* dst) {
         const int64_t r = b + tid;
         const int64_t rr = r < n ? r : n - 1;
-#pragma unroll
-        for (int c = 0; c < WPMAX; ++c) dst[c] = pc[c][rr];
+        sweep_load_row<WPMAX, RES, APPLY ? WPMAX : 16>(pc, rr, dst);
     };
     load_rows(chunk_base(blockIdx.x), pn);
     for (int64_t ci = blockIdx.x; ci < nch; ci += cstride) {
@@ -3479,6 +3499,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
 }
 
+// The sweeps' load policy as the launchers apply it.  CAL_SWEEP_RESIDENT is
+// the build-time default for same-box A/Bs (make variant
+// VFLAGS=-DCAL_SWEEP_RESIDENT=...): -2 follows the host's choice, -1 turns
+// the policy off, 0..3 replaces R wherever the host turns the policy on.
+#ifndef CAL_SWEEP_RESIDENT
+#define CAL_SWEEP_RESIDENT -2
+#endif
+static_assert(CAL_SWEEP_RESIDENT >= -2 && CAL_SWEEP_RESIDENT <= 3, "CAL_SWEEP_RESIDENT: -2, -1 or 0..3");
+static int sweep_res(int res) {
+    if (res < 0 || res > 3 || CAL_SWEEP_RESIDENT == -1) return -1;
+    return CAL_SWEEP_RESIDENT >= 0 ? CAL_SWEEP_RESIDENT : res;
+}
+// one launch per policy value (the policy kernels exist for three shapes only)
+#define CAL_RES_SWITCH(res, LAUNCH) \
+    switch (res) {                  \
+        case 0: LAUNCH(0); break;   \
+        case 1: LAUNCH(1); break;   \
+        case 2: LAUNCH(2); break;   \
+        case 3: LAUNCH(3); break;   \
+        default: LAUNCH(-1); break; \
+    }
+
 int rowapply_wpmax(int wp) { return wp <= 5 ? 5 : (wp <= 9 ? 9 : (wp <= 17 ? 17 : 0)); }
 int rowapply_mout(int m) { return m <= 4 ? 4 : (m <= 8 ? 8 : (m <= 16 ? 16 : 0)); }
 
@@ -3486,7 +3528,7 @@ int rowapply_mout(int m) { return m <= 4 ? 4 : (m <= 8 ? 8 : (m <= 16 ? 16 : 0))
 // 3 chained store (pass B).  Instantiated for the shapes of s = 4 and s = 8
 // ('full' with s = 4 reaches 10..17 projection columns with 4 outputs).
 hipError_t launch_rowapply(const ColList& P, const double* dM, int wp, int m, const OutList& Y, int kind, int wq,
-                           int64_t n, int blocks, double* partial, hipStream_t st, const double* gate) {
+                           int64_t n, int blocks, double* partial, hipStream_t st, const double* gate, int res) {
     const int WP = rowapply_wpmax(wp), MO = rowapply_mout(m);
     dim3 g(blocks), b(256);
     // pass B's block Q is read again only after the next step's matrix powers
@@ -3496,6 +3538,27 @@ hipError_t launch_rowapply(const ColList& P, const double* dM, int wp, int m, co
     // A/Bs: 817/818 -> 828/829 and 847/847/846 -> 855/854/855 outer-it/s,
     // profiles/r04/passb_nt/)
     const bool nts = (int64_t)n * 8 * (wp + m) > ((int64_t)256 << 20);
+    // the load policy: pass A and pass B of the 17 -> 8 block step (X =
+    // columns 9..16) only.  Its pass B stores non-temporally: the host turns
+    // the policy on for sweeps beyond the cache, where nts holds (the test
+    // build's switch also at small n: the store's policy changes no bits)
+    res = wp == 17 && m == 8 && (kind == 2 || kind == 3) ? sweep_res(res) : -1;
+    if (res >= 0) {
+#define CAL_RA_PASSA(R) \
+    hipLaunchKernelGGL((k_rowapply<17, 8, true, true, false, false, false, R>), g, b, 0, st, P, dM, wp, m, Y, wq, n, \
+                       partial, gate)
+#define CAL_RA_PASSB(R) \
+    hipLaunchKernelGGL((k_rowapply<17, 8, false, true, true, true, true, R>), g, b, 0, st, P, dM, wp, m, Y, wq, n, \
+                       partial, gate)
+        if (kind == 2) {
+            CAL_RES_SWITCH(res, CAL_RA_PASSA)
+        } else {
+            CAL_RES_SWITCH(res, CAL_RA_PASSB)
+        }
+#undef CAL_RA_PASSB
+#undef CAL_RA_PASSA
+        return hipGetLastError();
+    }
 #define CAL_RA(W, MM, G, S, C) \
     hipLaunchKernelGGL((k_rowapply<W, MM, G, true, S, C>), g, b, 0, st, P, dM, wp, m, Y, wq, n, partial, gate)
 #define CAL_RA_NT(W, MM) \
@@ -3743,11 +3806,17 @@ hipError_t launch_passb_wide(const ColList& P, const double* dM, const OutList& 
 
 // Row-parallel tile Gram: tile = P.p[0..nt) (nt <= 16), extra = P.p[16] if
 // has_extra.  Same partial layout as k_tilegram.
+// res: the load policy (k_rowapply RES), for the full tile [Qp(0:8) | X(8)]
+// with Qp's column 8 as the extra column only.
 hipError_t launch_rowgram(const ColList& P, int nt, bool has_extra, int64_t n, int blocks, double* partial,
-                          hipStream_t st) {
+                          hipStream_t st, int res) {
     OutList none{};
-    hipLaunchKernelGGL((k_rowapply<17, 4, true, false>), dim3(blocks), dim3(256), 0, st, P, nullptr, 17, nt, none,
-                       has_extra ? 1 : 0, n, partial, nullptr);
+    res = nt == 16 && has_extra ? sweep_res(res) : -1;
+#define CAL_RG(R)                                                                                                   \
+    hipLaunchKernelGGL((k_rowapply<17, 4, true, false, true, false, false, R>), dim3(blocks), dim3(256), 0, st, P, \
+                       nullptr, 17, nt, none, has_extra ? 1 : 0, n, partial, nullptr)
+    CAL_RES_SWITCH(res, CAL_RG)
+#undef CAL_RG
     return hipGetLastError();
 }
 

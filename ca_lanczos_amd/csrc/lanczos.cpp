@@ -1309,8 +1309,11 @@ int lanczos_step(cal_ctx* c, int diagnostics) {
                 c->pbw.qold = panel();
                 panel_add(c->pbw.qold, L.col(0), ld, (k - 2) * s);
             }
-            CAL_TRY(project_and_normalize_dev(c, n, Qp, X, true, Qo, Rq.data(), R.data(), &res));
+            c->sweep_x_fresh = true;  // X = V(:,2:s+1), the powers just written
+            const int st = project_and_normalize_dev(c, n, Qp, X, true, Qo, Rq.data(), R.data(), &res);
+            c->sweep_x_fresh = false;
             c->pbw.want = false;
+            CAL_TRY(st);
         }
         L.reorth.push_back(res.reorth ? 1 : 0);
         if (res.reorth) L.info.n_reorth++;
