@@ -473,6 +473,9 @@ static int sweep_policy(cal_ctx* c, int64_t n, int w, int m) {
 // The load policy the last device block orthogonalisation ran with (-1 off,
 // 0..3 resident columns; -2: none has run).
 extern "C" int cal_test_sweep_policy(cal_ctx* c) { return c ? c->test_sweep_res : -2; }
+// The coefficient source that block's pass A and pass B read (0 LDS, 1
+// uniform loads of M; -2: none has run).
+extern "C" int cal_test_sweep_coef(cal_ctx* c) { return c ? c->test_sweep_coef : -2; }
 namespace cal {
 #endif
 
@@ -502,6 +505,12 @@ static int orth_device(cal_ctx* c, int64_t n, const Panel& Qp, const Panel& X, b
     const int WP = rowapply_wpmax(wp), MO = rowapply_mout(m);
     const Panel W = panel_concat(Qp, X);
     const int res = sweep_policy(c, n, w, m);
+    // the sweeps' coefficient source: the launcher's choice, or the test
+    // build's switches (both sources give the same bits)
+    const int csrc = test_switch("CAL_TEST_SWEEP_COEF_LDS") ? 0 : (test_switch("CAL_TEST_SWEEP_COEF_SCALAR") ? 1 : -1);
+#ifdef CAL_TEST_HOOKS
+    c->test_sweep_coef = rowapply_coef(wp, m, 2, n, csrc);
+#endif
     CAL_TRY(ensure_red(c, 4096));
     double* d_tile = c->d_red;
     double* d_st = c->d_red + 1024;
@@ -561,7 +570,7 @@ static int orth_device(cal_ctx* c, int64_t n, const Panel& Qp, const Panel& X, b
     {
         const int t = timer_begin(c, 1, 8.0 * n * wp);
         CAL_HIP(c, launch_rowapply(cw, d_mbuf, wp, m, ol, 2, w, n, (int)blocks, c->d_partial, c->stream, nullptr,
-                                   res));
+                                   res, csrc));
         timer_end(c, t);
     }
     CAL_TRY(coef(1, 0));
@@ -600,7 +609,7 @@ static int orth_device(cal_ctx* c, int64_t n, const Panel& Qp, const Panel& X, b
     } else {
         const int t = timer_begin(c, 2, 8.0 * n * (wp + m));
         CAL_HIP(c, launch_rowapply(cw, d_mbuf, wp, m, ol, 3, w, n, (int)((n + 255) / 256), c->d_partial, c->stream,
-                                   gate, res));
+                                   gate, res, csrc));
         timer_end(c, t);
     }
     if (c->pre_wait) {  // e.g. the next step's matrix powers (lanczos_step)

@@ -325,9 +325,13 @@ struct OutList {
 // gate (kind 3): device flags; a nonzero gate[0] or gate[1] skips the store.
 // res: the sweep's load policy (kernels.hip k_rowapply RES; -1 = plain loads),
 // honoured by pass A and pass B of the 17 -> 8 block step.
+// coef: the coefficient source (k_rowapply COEF): -1 the launcher's choice,
+// 0 LDS, 1 uniform loads where a scalar-fed kernel exists; rowapply_coef
+// gives the source a launch with these arguments takes.
 hipError_t launch_rowapply(const ColList& P, const double* dM, int wp, int m, const OutList& Y, int kind, int wq,
                            int64_t n, int blocks, double* partial, hipStream_t st, const double* gate = nullptr,
-                           int res = -1);
+                           int res = -1, int coef = -1);
+int rowapply_coef(int wp, int m, int kind, int64_t n, int coef);
 // s x s coefficients of the two-sweep block orthogonalisation (phase 0 after
 // the P1 Gram, phase 1 after pass A); see kernels.hip k_orth_coef.
 // Phase 1 with hout != nullptr also publishes out (R, RY, flags; 516
@@ -636,6 +640,10 @@ struct cal_ctx {
     // orthogonalisation (blockorth.cpp sweep_policy), read back by
     // cal_test_sweep_policy; -2 before the first one
     int test_sweep_res = -2;
+    // the test build only: the coefficient source of that block's pass A and
+    // pass B (kernels.hip rowapply_coef: 0 LDS, 1 uniform loads), read back
+    // by cal_test_sweep_coef; -2 before the first one
+    int test_sweep_coef = -2;
 };
 
 // ---- helpers shared by the host-side translation units -----------------

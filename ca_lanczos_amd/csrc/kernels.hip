@@ -3286,9 +3286,14 @@ hipError_t launch_tilegram(const Panel& T, const double* E, int64_t n, int block
 }
 
 // k_rowapply: lane <-> row.  Y = P * M with P of wp <= WPMAX columns and
-// M zero-padded to WPMAX x MOUT (row-major), staged in LDS and read as
-// broadcasts (scalar loads of M measured 9 us faster for pass A alone but
-// slower for pass B, and no different in the loop).  Every column load is a
+// M zero-padded to WPMAX x MOUT (row-major).  COEF = 0: M is staged in LDS
+// and read as broadcasts, one row per panel column; COEF = 1: the rows are
+// read straight from the (block-uniform, read-only) argument M, which the
+// compiler turns into one uniform load per row with the FMAs taking the
+// scalar pair as an operand -- no LDS staging, and without the Gram no
+// block barrier.  The products, their order and the sums are the same, so
+// the source changes no bits (launch_rowapply chooses it).
+// Every column load is a
 // contiguous 512-B wave access; padded columns reload a valid column (cache
 // hit) times zero.
 // GRAM: the stored rows [Qp(0:nq) | Y(0:m)] (nq = min(wq, 8)) are
@@ -3308,6 +3313,15 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// Tuning knob of the scalar-fed sweeps (COEF = 1) for same-box A/Bs: the
+// accumulators are pinned every CAL_SWEEP_COEF_ROWS columns, so that many
+// uniform row loads (16 SGPRs each) are in flight together.  The FMA order
+// per accumulator does not depend on it.
+#ifndef CAL_SWEEP_COEF_ROWS
+#define CAL_SWEEP_COEF_ROWS 4
+#endif
+static_assert(CAL_SWEEP_COEF_ROWS >= 1 && CAL_SWEEP_COEF_ROWS <= 4, "CAL_SWEEP_COEF_ROWS: 1..4");
 
 // RES (the load policy of a sweep too large for the Infinity Cache, chosen by
 // blockorth.cpp sweep_policy): -1 plain loads; 0..3: every column is loaded
@@ -3335,7 +3349,7 @@ __device__ __forceinline__ void sweep_load_row(const double* const* pc, int64_t 
 // redoes the block from its input -- which, in ca_lanczos's first block, is
 // the same storage as the output (q = Q(:,1)).
 template <int WPMAX, int MOUT, bool GRAM, bool APPLY = true, bool STORE = true, bool CHAIN = false, bool NTS = false,
-          int RES = -1>
+          int RES = -1, int COEF = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_rowapply(ColList P, const double* __restrict__ M, int wp, int m,
                                                   OutList Y, int wq, int64_t n, double* __restrict__ partial,
                                                   const double* __restrict__ gate) {
@@ -3347,16 +3361,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     // (38 KB per block -> 4 blocks per CU)
     __shared__ double tile[GRAM ? 256 * TLD : 1];
     double* const red = tile;
-    __shared__ __attribute__((aligned(16))) double Ms[MSZ];  // broadcast reads
+    __shared__ __attribute__((aligned(16))) double Ms[COEF ? 2 : MSZ];  // broadcast reads
+    const double* const Mc = COEF ? M : Ms;  // the coefficient rows' source
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c16 = lane & 15, g = lane >> 4;
     const int nq = wq < 8 ? wq : 8;
     const bool has_ext = wq > 8;
-    if (APPLY)
+    if (APPLY && !COEF)
         for (int e = tid; e < MSZ; e += 256) Ms[e] = M[e];
     if (GRAM)
         for (int e = tid; e < 256 * TLD; e += 256) tile[e] = 0.0;
-    __syncthreads();
+    if (GRAM || !COEF) __syncthreads();
     d4 acc = d4{0.0, 0.0, 0.0, 0.0};
     double eacc = 0.0;
     // (host pads P.p[c >= wp] with a valid column and Y.p[j >= m] unused)
@@ -3396,12 +3411,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
             // the accumulators as operands, so column c's FMAs retire before
             // column c+1's broadcasts issue (otherwise the scheduler keeps all
             // WPMAX*MOUT M values live and spills)
+            if (!COEF || c % CAL_SWEEP_COEF_ROWS == 0) {
 #pragma unroll
-            for (int j = 0; j < MOUT; ++j) asm volatile("" : "+v"(y[j])::"memory");
+                for (int j = 0; j < MOUT; ++j) asm volatile("" : "+v"(y[j])::"memory");
+            }
             double mrow[MOUT];
 #pragma unroll
             for (int j = 0; j < MOUT; j += 2) {
-                const d2 t = *reinterpret_cast<const d2*>(&Ms[c * MOUT + j]);
+                const d2 t = *reinterpret_cast<const d2*>(&Mc[c * MOUT + j]);
                 mrow[j] = t[0];
                 if (j + 1 < MOUT) mrow[j + 1] = t[1];
             }
@@ -3410,15 +3427,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         }
         if (CHAIN) {
             // y2 = P(0:wq) * M2p + y * M2y  (same pinning as above)
-            const double* M2p = Ms + WPMAX * MOUT;
-            const double* M2y = Ms + 2 * WPMAX * MOUT;
+            const double* M2p = Mc + WPMAX * MOUT;
+            const double* M2y = Mc + 2 * WPMAX * MOUT;
             double y2[MOUT];
 #pragma unroll
             for (int j = 0; j < MOUT; ++j) y2[j] = 0.0;
 #pragma unroll
             for (int c = 0; c < WPMAX + MOUT; ++c) {
+                if (!COEF || c % CAL_SWEEP_COEF_ROWS == 0) {
 #pragma unroll
-                for (int j = 0; j < MOUT; ++j) asm volatile("" : "+v"(y2[j])::"memory");
+                    for (int j = 0; j < MOUT; ++j) asm volatile("" : "+v"(y2[j])::"memory");
+                }
                 const double src = c < WPMAX ? p[c < WPMAX ? c : 0] : y[c >= WPMAX ? c - WPMAX : 0];
                 const double* row = c < WPMAX ? M2p + c * MOUT : M2y + (c - WPMAX) * MOUT;
                 double mrow[MOUT];
@@ -3524,12 +3543,41 @@ static int sweep_res(int res) {
 int rowapply_wpmax(int wp) { return wp <= 5 ? 5 : (wp <= 9 ? 9 : (wp <= 17 ? 17 : 0)); }
 int rowapply_mout(int m) { return m <= 4 ? 4 : (m <= 8 ? 8 : (m <= 16 ? 16 : 0)); }
 
+// The sweeps' coefficient source (k_rowapply COEF): 0 the LDS-staged table,
+// 1 uniform loads of M.  The scalar-fed kernels exist for pass A and pass B
+// (kinds 2 and 3) of the 17 x 8 instantiation; every other shape and kind
+// reads LDS.  By default the block step at the size the sweeps stream at
+// (pass B storing non-temporally, with or without the load policy) takes the
+// scalar source and sweeps the Infinity Cache holds keep LDS.
+// CAL_SWEEP_COEF is the build-time default for same-box A/Bs (make variant
+// VFLAGS=-DCAL_SWEEP_COEF=0|1): 0 LDS everywhere, 1 scalar wherever a
+// scalar-fed kernel exists; coef >= 0 (the test build's switch) does the same
+// per launch.
+#ifndef CAL_SWEEP_COEF
+#define CAL_SWEEP_COEF -1
+#endif
+static_assert(CAL_SWEEP_COEF >= -1 && CAL_SWEEP_COEF <= 1, "CAL_SWEEP_COEF: -1, 0 or 1");
+// the kinds the default choice moves to the scalar source (bit 0 pass A, bit
+// 1 pass B; -DCAL_SWEEP_COEF_KINDS=1|2|3 for A/Bs of one pass alone)
+#ifndef CAL_SWEEP_COEF_KINDS
+#define CAL_SWEEP_COEF_KINDS 3
+#endif
+int rowapply_coef(int wp, int m, int kind, int64_t n, int coef) {
+    if (rowapply_wpmax(wp) != 17 || rowapply_mout(m) != 8 || (kind != 2 && kind != 3)) return 0;
+    if (coef < 0) coef = CAL_SWEEP_COEF;
+    if (coef >= 0) return coef ? 1 : 0;
+    if (!((CAL_SWEEP_COEF_KINDS >> (kind - 2)) & 1)) return 0;
+    return (int64_t)n * 8 * (wp + m) > ((int64_t)256 << 20) ? 1 : 0;  // (pass B's nts)
+}
+
 // kind: 0 store only, 1 store + Gram, 2 Gram without store (pass A),
 // 3 chained store (pass B).  Instantiated for the shapes of s = 4 and s = 8
 // ('full' with s = 4 reaches 10..17 projection columns with 4 outputs).
 hipError_t launch_rowapply(const ColList& P, const double* dM, int wp, int m, const OutList& Y, int kind, int wq,
-                           int64_t n, int blocks, double* partial, hipStream_t st, const double* gate, int res) {
+                           int64_t n, int blocks, double* partial, hipStream_t st, const double* gate, int res,
+                           int coef) {
     const int WP = rowapply_wpmax(wp), MO = rowapply_mout(m);
+    coef = rowapply_coef(wp, m, kind, n, coef);
     dim3 g(blocks), b(256);
     // pass B's block Q is read again only after the next step's matrix powers
     // have streamed through the Infinity Cache (256 MB): when the sweep's
@@ -3543,22 +3591,41 @@ hipError_t launch_rowapply(const ColList& P, const double* dM, int wp, int m, co
     // the policy on for sweeps beyond the cache, where nts holds (the test
     // build's switch also at small n: the store's policy changes no bits)
     res = wp == 17 && m == 8 && (kind == 2 || kind == 3) ? sweep_res(res) : -1;
-    if (res >= 0) {
 #define CAL_RA_PASSA(R) \
     hipLaunchKernelGGL((k_rowapply<17, 8, true, true, false, false, false, R>), g, b, 0, st, P, dM, wp, m, Y, wq, n, \
                        partial, gate)
 #define CAL_RA_PASSB(R) \
     hipLaunchKernelGGL((k_rowapply<17, 8, false, true, true, true, true, R>), g, b, 0, st, P, dM, wp, m, Y, wq, n, \
                        partial, gate)
+#define CAL_RA_PASSA_S(R) \
+    hipLaunchKernelGGL((k_rowapply<17, 8, true, true, false, false, false, R, 1>), g, b, 0, st, P, dM, wp, m, Y, wq, n, \
+                       partial, gate)
+#define CAL_RA_PASSB_S(R) \
+    hipLaunchKernelGGL((k_rowapply<17, 8, false, true, true, true, true, R, 1>), g, b, 0, st, P, dM, wp, m, Y, wq, n, \
+                       partial, gate)
+    if (coef) {  // the scalar-fed pass A and pass B (17 x 8), with or without the load policy
+        if (kind == 2) {
+            CAL_RES_SWITCH(res, CAL_RA_PASSA_S)
+        } else if (res >= 0 || nts) {
+            CAL_RES_SWITCH(res, CAL_RA_PASSB_S)
+        } else {
+            hipLaunchKernelGGL((k_rowapply<17, 8, false, true, true, true, false, -1, 1>), g, b, 0, st, P, dM, wp, m, Y,
+                               wq, n, partial, gate);
+        }
+        return hipGetLastError();
+    }
+    if (res >= 0) {
         if (kind == 2) {
             CAL_RES_SWITCH(res, CAL_RA_PASSA)
         } else {
             CAL_RES_SWITCH(res, CAL_RA_PASSB)
         }
-#undef CAL_RA_PASSB
-#undef CAL_RA_PASSA
         return hipGetLastError();
     }
+#undef CAL_RA_PASSB_S
+#undef CAL_RA_PASSA_S
+#undef CAL_RA_PASSB
+#undef CAL_RA_PASSA
 #define CAL_RA(W, MM, G, S, C) \
     hipLaunchKernelGGL((k_rowapply<W, MM, G, true, S, C>), g, b, 0, st, P, dM, wp, m, Y, wq, n, partial, gate)
 #define CAL_RA_NT(W, MM) \

@@ -13,10 +13,31 @@
 //   hipcc -O3 --offload-arch=gfx950 tools/residency_probe.hip -o tools/residency_probe
 // One JSON line per variant and pass; the whole list runs PASSES times so the
 // spread of RES = -1 within the process is on record.
+//   tools/residency_probe coef
+// runs, in the library shape at RES = 3 only, the attribution of what the
+// library's pass A and pass B do besides loading their 17 columns
+// (k_sweep17c: each knob puts back one thing k_rowapply has and k_sweep17
+// lacks), twice per process, one JSON line per variant and pass:
+//   coef   imm: immediate coefficients; lds: an LDS-staged table read one
+//          row per column behind the library's pins (a); glb: uniform loads
+//          of a global table behind the same pins (b)
+//   gramt  the second sweep with the wave's 64-row LDS transpose, 16
+//          v_mfma_f64_16x16x4f64 per chunk and the extra VALU column (c;
+//          with coef lds: d, pass A as it is; with coef glb: e)
+//   chain  the apply sweep with pass B's 17 + 25 coefficient rows
+// The first sweep (P1 has no coefficients) is always k_sweep17's.
+// -DSWEEP_COEF_ROWS=r (1..4, default 4): coef glb pins its accumulators every r columns,
+// so r uniform row loads are in flight together (k_rowapply's
+// CAL_SWEEP_COEF_ROWS).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <string>
 #include <vector>
+
+#ifndef SWEEP_COEF_ROWS
+#define SWEEP_COEF_ROWS 4
+#endif
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP %s line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
@@ -150,6 +171,162 @@ __global__ __launch_bounds__(256) void k_sweep17(Col17 P, Col8 Y, int64_t n) {
     }
 }
 
+// The attribution variants (RES = 3, one row per lane).  COEF: 0 immediates,
+// 1 LDS table, 2 uniform loads of M; the table is k_rowapply's
+// [M1 (17 x 8) | M2p (17 x 8) | M2y (8 x 8)], row-major.
+typedef double d4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <int COEF>
+__device__ __forceinline__ void coef_row(const double* Mc, int row, double* mrow) {
+    if constexpr (COEF == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mrow[j] = 0.01 * (row % 25 + j);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            const d2 t = *reinterpret_cast<const d2*>(&Mc[row * 8 + j]);
+            mrow[j] = t[0];
+            mrow[j + 1] = t[1];
+        }
+    }
+}
+template <int COEF, bool GRAMT, bool STORE, bool CHAIN, bool LOOP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_sweep17c(Col17 P, Col8 Y, const double* __restrict__ M,
+                                                  double* __restrict__ partial, int64_t n) {
+    constexpr int RES = 3, TLD = 17, MSZ = 17 * 8 * 2 + 64;
+    __shared__ double tile[GRAMT ? 256 * TLD : 1];
+    __shared__ __attribute__((aligned(16))) double Ms[COEF == 1 ? MSZ : 2];
+    const double* const Mc = COEF == 1 ? Ms : M;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c16 = lane & 15, g = lane >> 4;
+    if (COEF == 1)
+        for (int e = tid; e < MSZ; e += 256) Ms[e] = M[e];
+    if (GRAMT)
+        for (int e = tid; e < 256 * TLD; e += 256) tile[e] = 0.0;
+    if (COEF == 1 || GRAMT) __syncthreads();
+    const int64_t nch = (n + 255) / 256;
+    const int64_t cstride = LOOP ? (int64_t)gridDim.x : nch;
+    d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+    double eacc = 0.0;
+    double y[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = 0.0;
+    double pn[17];
+    {
+        const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+        load17<RES, double>(P, r < n ? r : n - 1, pn);
+    }
+    for (int64_t ci = blockIdx.x; ci < nch; ci += cstride) {
+        asm volatile("" ::: "memory");
+        const int64_t r = ci * 256 + tid;
+        const bool in = r < n;
+        double v[17];
+#pragma unroll
+        for (int c = 0; c < 17; ++c) v[c] = in ? pn[c] : 0.0;
+        if (LOOP && ci + cstride < nch) {
+            const int64_t r2 = (ci + cstride) * 256 + tid;
+            load17<RES, double>(P, r2 < n ? r2 : n - 1, pn);
+        }
+        if (STORE || GRAMT) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) y[j] = 0.0;
+        }
+#pragma unroll
+        for (int c = 0; c < 17; ++c) {
+            if (COEF != 2 || c % SWEEP_COEF_ROWS == 0) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(y[j])::"memory");
+            }
+            double mrow[8];
+            coef_row<COEF>(Mc, c, mrow);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) y[j] = __builtin_fma(v[c], mrow[j], y[j]);
+        }
+        if (CHAIN) {
+            double y2[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) y2[j] = 0.0;
+#pragma unroll
+            for (int c = 0; c < 25; ++c) {
+                if (COEF != 2 || c % SWEEP_COEF_ROWS == 0) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(y2[j])::"memory");
+                }
+                const double src = c < 17 ? v[c < 17 ? c : 0] : y[c >= 17 ? c - 17 : 0];
+                double mrow[8];
+                coef_row<COEF>(Mc, 17 + c, mrow);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) y2[j] = __builtin_fma(src, mrow[j], y2[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) y[j] = y2[j];
+        }
+        if (STORE && in) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) __builtin_nontemporal_store(y[j], Y.p[j] + r);
+        }
+        if (GRAMT) {
+            double* trow = tile + tid * TLD;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) trow[c] = v[c];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) trow[8 + j] = y[j];
+            trow[16] = v[8];
+            wave_lds_sync();
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int row = wave * 64 + 4 * k + g;
+                const double a = tile[row * TLD + c16];
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc, 0, 0, 0);
+                eacc = eacc + tile[row * TLD + 16] * a;
+            }
+            wave_lds_sync();
+        }
+    }
+    if constexpr (GRAMT) {  // the block's partials, as k_rowapply writes them (272 entries x gridDim.x)
+        double* const red = tile;
+        __syncthreads();
+        if (wave > 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) red[((wave - 1) * 64 + lane) * 5 + q] = acc[q];
+            red[((wave - 1) * 64 + lane) * 5 + 4] = eacc;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int64_t nb = gridDim.x;
+            double* out = partial + blockIdx.x;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                double s = acc[q];
+                for (int w = 0; w < 3; ++w) s = s + red[(w * 64 + lane) * 5 + q];
+                out[(int64_t)(c16 * 16 + g + 4 * q) * nb] = s;
+            }
+            double e = eacc;
+            for (int w = 0; w < 3; ++w) e = e + red[(w * 64 + lane) * 5 + 4];
+            const double e1 = __shfl(e, c16 + 16, 64), e2 = __shfl(e, c16 + 32, 64), e3 = __shfl(e, c16 + 48, 64);
+            if (g == 0) out[(int64_t)(256 + c16) * nb] = ((e + e1) + e2) + e3;
+        }
+    } else if constexpr (!STORE) {
+        if (y[0] == 1.2345) Y.p[0][(int64_t)blockIdx.x * 256 + tid] = y[1];
+    }
+}
+
+// second sweep (1024 blocks, grid-stride) and apply sweep (one row per thread) of one attribution variant
+template <int COEF>
+static void sweep_c(bool second, bool knob, int grid, const Col17& P, const Col8& Y, const double* M, double* partial,
+                    int64_t n) {
+    if (second) {
+        if (knob) hipLaunchKernelGGL((k_sweep17c<COEF, true, false, false, true>), dim3(grid), dim3(256), 0, 0, P, Y, M, partial, n);
+        else hipLaunchKernelGGL((k_sweep17c<COEF, false, false, false, true>), dim3(grid), dim3(256), 0, 0, P, Y, M, partial, n);
+    } else {
+        if (knob) hipLaunchKernelGGL((k_sweep17c<COEF, false, true, true, false>), dim3(grid), dim3(256), 0, 0, P, Y, M, partial, n);
+        else hipLaunchKernelGGL((k_sweep17c<COEF, false, true, false, false>), dim3(grid), dim3(256), 0, 0, P, Y, M, partial, n);
+    }
+}
+
 template <bool STORE, bool LASTPLAIN, bool LOOP, int ROWS>
 static void sweep(int res, int grid, const Col17& P, const Col8& Y, int64_t n) {
     switch (res) {
@@ -166,7 +343,8 @@ static void sweep(int rows, int res, int grid, const Col17& P, const Col8& Y, in
     else sweep<STORE, LASTPLAIN, LOOP, 1>(res, grid, P, Y, n);
 }
 
-int main() {
+int main(int argc, char** argv) {
+    const bool coef_mode = argc > 1 && std::string(argv[1]) == "coef";
     const int N = 215;
     const int64_t n = (int64_t)N * N * N, P = (int64_t)N * N;
     uint16_t* id;
@@ -222,6 +400,65 @@ int main() {
             for (int lp = 0; lp < 2; ++lp)
                 for (int res = -1; res <= 3; ++res) vs.push_back({form, rows, res, lp});
     const int PASSES = 4, steps = 6;
+    if (coef_mode) {
+        // the coefficient table (the emulation's immediates) and the Gram partials
+        constexpr int MSZ = 17 * 8 * 2 + 64;
+        std::vector<double> hm(MSZ);
+        for (int row = 0; row < 42; ++row)
+            for (int j = 0; j < 8; ++j) hm[row * 8 + j] = 0.01 * (row % 25 + j);
+        double *gm, *gpart;
+        CK(hipMalloc(&gm, MSZ * 8));
+        CK(hipMemcpy(gm, hm.data(), MSZ * 8, hipMemcpyHostToDevice));
+        CK(hipMalloc(&gpart, (size_t)1024 * 272 * 8));
+        const int ga = (int)((n + 255) / 256);
+        const char* cname[3] = {"imm", "lds", "glb"};
+        for (int pass = 0; pass < 2; ++pass) {
+            // ref: k_sweep17 in all three sweeps (the line "lib x1 res 3" of the full list)
+            for (int vi = -1; vi < 12; ++vi) {
+                const int coef = vi < 0 ? 0 : vi / 4, gramt = vi < 0 ? 0 : (vi >> 1) & 1, chain = vi < 0 ? 0 : vi & 1;
+                double acc[11] = {0};
+                for (int stp = 0; stp < steps; ++stp) {
+                    CK(hipEventRecord(ev[0]));
+                    for (int j = 0; j < 8; ++j) {
+                        hipLaunchKernelGGL(k_pairtab, dim3(g2), dim3(256), 0, 0, V(j), V(j + 1), id, n, go, gv);
+                        CK(hipEventRecord(ev[j + 1]));
+                    }
+                    sweep<false, false, true>(1, 3, 1024, Pc, Yc, n);
+                    CK(hipEventRecord(ev[9]));
+                    if (vi < 0) sweep<false, false, true>(1, 3, 1024, Pc, Yc, n);
+                    else if (coef == 0) sweep_c<0>(true, gramt, 1024, Pc, Yc, gm, gpart, n);
+                    else if (coef == 1) sweep_c<1>(true, gramt, 1024, Pc, Yc, gm, gpart, n);
+                    else sweep_c<2>(true, gramt, 1024, Pc, Yc, gm, gpart, n);
+                    CK(hipEventRecord(ev[10]));
+                    if (vi < 0) sweep<true, false, false>(1, 3, ga, Pc, Yc, n);
+                    else if (coef == 0) sweep_c<0>(false, chain, ga, Pc, Yc, gm, gpart, n);
+                    else if (coef == 1) sweep_c<1>(false, chain, ga, Pc, Yc, gm, gpart, n);
+                    else sweep_c<2>(false, chain, ga, Pc, Yc, gm, gpart, n);
+                    CK(hipEventRecord(ev[11]));
+                    CK(hipEventSynchronize(ev[11]));
+                    CK(hipGetLastError());
+                    if (stp == 0) continue;
+                    for (int k = 0; k < 11; ++k) {
+                        float ms;
+                        CK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+                        acc[k] += ms * 1e3 / (steps - 1);
+                    }
+                }
+                double tot = 0;
+                for (int k = 0; k < 11; ++k) tot += acc[k];
+                if (vi < 0) printf("{\"inloop\": \"lib x1 res 3\", \"variant\": \"ref\", ");
+                else printf("{\"inloop\": \"lib x1 res 3 coef %s%s%s\", \"variant\": \"sweep17c\", \"coef\": \"%s\", \"gramt\": %d, \"chain\": %d, ",
+                            cname[coef], gramt ? " gramt" : "", chain ? " chain" : "", cname[coef], gramt, chain);
+                printf("\"pass\": %d, \"spmv_us\": [", pass);
+                for (int k = 0; k < 8; ++k) printf("%.1f%s", acc[k], k < 7 ? ", " : "");
+                printf("], \"gram_us\": %.1f, \"gram2_us\": %.1f, \"apply_us\": %.1f, \"total_us\": %.1f}\n", acc[8], acc[9],
+                       acc[10], tot);
+                fflush(stdout);
+            }
+        }
+        CK(hipDeviceSynchronize());
+        return 0;
+    }
     for (int pass = 0; pass < PASSES; ++pass) {
         for (const Variant& vr : vs) {
             double acc[11] = {0};
