@@ -203,6 +203,28 @@ class Context:
                                            ctypes.cast(ctypes.byref(n2), dp)), "prop_combine")
         return ore + 1j * oim, n2.value
 
+    def prop_combine_obs(self, Q, c, W=None, phi=None):
+        """``prop_combine`` through the kernel that also reduces observables
+        (cal_prop_combine_obs): W real diagonal operators (a list or n x nw),
+        phi complex reference states (a list or n x nphi), at most 4 each.
+        Returns (out, norm2, <W_k> = sum W_k |out|^2 (nw), <phi_r|out> (nphi,
+        complex)); out and norm2 have the bits of ``prop_combine``."""
+        Q = f64(Q)
+        n, m = Q.shape[0] // 2, Q.shape[1]
+        c = np.asarray(c, dtype=np.complex128).ravel()
+        cre, cim = np.ascontiguousarray(c.real), np.ascontiguousarray(c.imag)
+        Wm, pre, pim = _obs_arrays(n, W, phi)
+        nw, nphi = Wm.shape[1], pre.shape[1]
+        ore, oim = np.zeros(n), np.zeros(n)
+        sums = np.zeros(max(nw + 2 * nphi, 1))
+        n2 = ctypes.c_double()
+        check(self.h, lib.cal_prop_combine_obs(self.h, n, m, ptr(Q), ptr(cre), ptr(cim), nw, ptr(Wm) if nw else None,
+                                               nphi, ptr(pre) if nphi else None, ptr(pim) if nphi else None,
+                                               ptr(ore), ptr(oim), ctypes.cast(ctypes.byref(n2), dp), ptr(sums)),
+              "prop_combine_obs")
+        ov = sums[nw:nw + 2 * nphi]
+        return ore + 1j * oim, n2.value, sums[:nw].copy(), ov[0::2] + 1j * ov[1::2]
+
     def set_matrix_csc(self, A):
         """MATLAB's sparse storage (mxGetJc / mxGetIr / mxGetPr: CSC with int64
         mwIndex arrays) through cal_set_matrix_csc, the entry a MEX shim uses."""
@@ -834,14 +856,33 @@ def _eigest(eigest):
     return e, len(e)
 
 
+def _obs_arrays(n, W, phi):
+    """(W n x nw, Re phi n x nphi, Im phi n x nphi), column-major float64, from lists or 2-D arrays."""
+    def cols(a, dtype):
+        if a is None or len(a) == 0:
+            return np.zeros((n, 0), dtype=dtype)
+        a = np.asarray(a, dtype=dtype) if not isinstance(a, (list, tuple)) else np.column_stack(
+            [np.asarray(x, dtype=dtype).ravel() for x in a])
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim != 2 or a.shape[0] != n:
+            raise ValueError("observables need n rows (one column per operator or reference state)")
+        return a
+    Wm = f64(cols(W, np.float64))
+    p = cols(phi, np.complex128)
+    return Wm, f64(p.real), f64(p.imag)
+
+
 class Propagator:
     """Time stepper ``psi <- exp(-i dt H) psi`` for a real symmetric sparse H
     and a complex state (cal_prop_*; ca_lanczos_prop.m as runLanczos.m:84-131
     drives it).  H is embedded as blkdiag(H, H) and the state lives on the
-    device as [Re psi; Im psi]; ``state()`` is the only copy back."""
+    device as [Re psi; Im psi]; ``state()`` is the only copy back of the
+    state, ``set_observables`` / ``observables`` watch it from the device."""
 
     def __init__(self, H, psi0, s, max_blocks, basis="newton", eigest=None, ctx=None):
         self.n = H.shape[0]
+        self._nw = 0
         self._own = ctx is None
         self.ctx = ctx or Context()
         try:
@@ -875,6 +916,40 @@ class Propagator:
         return dict(steps=i.steps, lsteps=i.lsteps, lsteps_max=i.lsteps_max, lsteps_sum=i.lsteps_sum,
                     residual=i.residual, residual_max=i.residual_max, norm=i.norm,
                     shifts=np.array(i.shifts[:i.nshifts]), breakdowns=i.breakdowns, rank_deficient=i.rank_deficient, ms=i.ms)
+
+    def set_observables(self, W=None, phi=None, energy=False):
+        """Record, after every later time step and without copying the state
+        back: ``sum W_k |psi|^2`` for real diagonal operators W (a list or
+        n x nw, at most 4), ``<phi_r|psi>`` for complex reference states phi
+        (a list or n x nphi, at most 4) and, with ``energy``, ``<psi|H|psi>``
+        (one more SpMV per step).  Replaces an earlier set and clears the
+        history; no arguments switch the observables off."""
+        if not getattr(self, "_open", False):
+            raise CalError(_lib.CAL_ERR_ARG, "set_observables: the propagator is closed")
+        Wm, pre, pim = _obs_arrays(self.n, W, phi)
+        nw, nphi = Wm.shape[1], pre.shape[1]
+        check(self.ctx.h, lib.cal_prop_set_observables(self.ctx.h, nw, ptr(Wm) if nw else None, nphi,
+                                                       ptr(pre) if nphi else None, ptr(pim) if nphi else None,
+                                                       1 if energy else 0), "prop_set_observables")
+        self._nw = nw
+        return self
+
+    def observables(self, first=0, count=None):
+        """The history since ``set_observables``, one entry per completed
+        step (rows [first, first + count); default all): dict of ``t``,
+        ``norm2``, ``energy`` (NaN when off), ``W`` (steps x nw) and
+        ``overlap`` (steps x nphi, complex)."""
+        nr, nc = ctypes.c_int64(), ctypes.c_int()
+        check(self.ctx.h, lib.cal_prop_get_observables(self.ctx.h, 0, 0, None, ctypes.byref(nr), ctypes.byref(nc)),
+              "prop_get_observables")
+        count = nr.value - first if count is None else count
+        rows = np.zeros((max(count, 0), nc.value))
+        check(self.ctx.h, lib.cal_prop_get_observables(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr),
+                                                       ctypes.byref(nc)), "prop_get_observables")
+        nw = self._nw  # the W columns come first, then the (Re, Im) pairs
+        ov = rows[:, 3 + nw:]
+        return dict(t=rows[:, 0].copy(), norm2=rows[:, 1].copy(), energy=rows[:, 2].copy(),
+                    W=rows[:, 3:3 + nw].copy(), overlap=ov[:, 0::2] + 1j * ov[:, 1::2])
 
     def close(self):
         if getattr(self, "_open", False):

@@ -518,6 +518,24 @@ constexpr int kPropMaxCols = 512;
 int prop_combine_blocks(int64_t n);
 hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
                                double* out, double* partial, hipStream_t st);
+// The same sweep with observables of the new state (k_prop_combine's OBS
+// flag): nw <= kPropMaxObs real diagonal operators W(:, k) and np <=
+// kPropMaxObs reference states pr(:, r) + i pi(:, r), column-major with the
+// even leading dimension ld >= n and 16-byte-aligned origins.  Quantity q's
+// block partials are partial[q * blocks + block], blocks =
+// prop_combine_blocks(n) (launch_reduce(partial, blocks, 1 + nw + 2 np, ...)
+// sums them all): q = 0 the squared norm (the bits of launch_prop_combine),
+// 1 + k sum W_k |psi'|^2, 1 + nw + 2r and + 2r + 1 Re and Im <phi_r|psi'>.
+constexpr int kPropMaxObs = 4;
+struct PropObs {
+    const double* W = nullptr;
+    const double* pr = nullptr;
+    const double* pi = nullptr;
+    int64_t ld = 0;
+    int nw = 0, np = 0;
+};
+hipError_t launch_prop_combine_obs(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
+                                   double* out, double* partial, const PropObs& o, hipStream_t st);
 
 
 }  // namespace cal

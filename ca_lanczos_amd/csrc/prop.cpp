@@ -42,9 +42,20 @@ struct PropState {
     std::vector<double> shifts;  // Leja order
     double* d_psi = nullptr;     // one vector column (A.ld doubles, local origin at +lpad)
     double* d_coef = nullptr;    // a (kPropMaxCols) then b
-    double* h_coef = nullptr;    // pinned; [2 kPropMaxCols] receives the squared norm
+    double* h_coef = nullptr;    // pinned; [2 kPropMaxCols] on receives the squared norm (then the observables)
     double nrm2 = 0.0;           // psi'psi
     cal_prop_info info{};
+    double t = 0.0;              // the accumulated time, sum of dt over the completed steps
+    // observables (cal_prop_set_observables): reduced in the combine sweep
+    int nw = 0, nphi = 0;
+    bool energy = false;
+    double* d_obs = nullptr;     // W (nw columns), phi_re (nphi), phi_im (nphi); ldo doubles each
+    int64_t ldo = 0;             // even, >= n
+    double* d_hpsi = nullptr;    // energy: H psi (one vector column, A.ld doubles)
+    int eparts = 0;              // energy: mode 4's partials (0: SpMV + dot)
+    std::vector<double> hist;    // one row of 3 + nw + 2 nphi per completed step
+    bool obs_on() const { return nw > 0 || nphi > 0 || energy; }
+    int nq() const { return nw + 2 * nphi; }
     double* psi(const cal_ctx* c) const { return d_psi + c->A.lpad; }
 };
 
@@ -54,8 +65,19 @@ double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+void obs_free(PropState& P) {
+    if (P.d_obs) hipFree(P.d_obs);
+    if (P.d_hpsi) hipFree(P.d_hpsi);
+    P.d_obs = P.d_hpsi = nullptr;
+    P.nw = P.nphi = P.eparts = 0;
+    P.ldo = 0;
+    P.energy = false;
+    P.hist.clear();
+}
+
 void prop_free(cal_ctx* c) {
     if (!c || !c->prop) return;
+    obs_free(*c->prop);
     if (c->prop->d_psi) hipFree(c->prop->d_psi);
     if (c->prop->d_coef) hipFree(c->prop->d_coef);
     if (c->prop->h_coef) hipHostFree(c->prop->h_coef);
@@ -70,19 +92,71 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     CAL_HIP_OTHER(c, hipMemcpyAsync(P.d_coef, P.h_coef, 2 * kPropMaxCols * sizeof(double), hipMemcpyHostToDevice,
                                     c->stream));
     const int nb = prop_combine_blocks(P.n);
-    CAL_TRY(ensure_partial(c, nb));
-    CAL_TRY(ensure_red(c, 1));
-    const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n) * 8.0);
-    const hipError_t e =
-        launch_prop_combine(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c), c->d_partial, c->stream);
+    if (!P.obs_on()) {
+        CAL_TRY(ensure_partial(c, nb));
+        CAL_TRY(ensure_red(c, 1));
+        const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n) * 8.0);
+        const hipError_t e =
+            launch_prop_combine(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c), c->d_partial, c->stream);
+        timer_end(c, t);
+        if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
+        CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1, c->d_red, c->stream));
+        CAL_HIP_OTHER(c, hipMemcpyAsync(P.h_coef + 2 * kPropMaxCols, c->d_red, sizeof(double), hipMemcpyDeviceToHost,
+                                        c->stream));
+        CAL_HIP(c, hipStreamSynchronize(c->stream));
+        P.nrm2 = P.h_coef[2 * kPropMaxCols];
+        return 0;
+    }
+    // with observables: d_red = [psi'psi, the nw + 2 nphi sums, the energy],
+    // fetched with the squared norm in the one pinned transfer
+    const int nq = P.nq();
+    const int nd = dot_blocks(2 * P.n);
+    const size_t pe = (size_t)(1 + nq) * nb;  // the energy's partials follow the combine's
+    CAL_TRY(ensure_partial(c, pe + (size_t)std::max(P.eparts, nd)));
+    CAL_TRY(ensure_red(c, (size_t)nq + 2));
+    PropObs o;
+    o.W = P.d_obs;
+    o.pr = P.d_obs + (size_t)P.nw * P.ldo;
+    o.pi = P.d_obs + (size_t)(P.nw + P.nphi) * P.ldo;
+    o.ld = P.ldo;
+    o.nw = P.nw;
+    o.np = P.nphi;
+    const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n + (double)P.n * (P.nw + 2 * P.nphi)) * 8.0);
+    const hipError_t e = launch_prop_combine_obs(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c),
+                                                 c->d_partial, o, c->stream);
     timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1, c->d_red, c->stream));
-    CAL_HIP_OTHER(c, hipMemcpyAsync(P.h_coef + 2 * kPropMaxCols, c->d_red, sizeof(double), hipMemcpyDeviceToHost,
-                                    c->stream));
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine_obs");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1 + nq, c->d_red, c->stream));
+    if (P.energy) {
+        // <psi'|H|psi'> = y'x over the stacked rows, y = blkdiag(H, H) x: the
+        // fused Lanczos mode's dot, reduced as lanczos_std.cpp reduces it
+        double* y = P.d_hpsi + c->A.lpad;
+        double* part = c->d_partial + pe;
+        if (P.eparts > 0) {
+            CAL_TRY(spmv_lanczos_dev(c, P.psi(c), nullptr, nullptr, y, part));
+            CAL_HIP_OTHER(c, launch_reduce(part, P.eparts, 1, c->d_red + 1 + nq, c->stream));
+        } else {
+            CAL_TRY(spmv_dev(c, P.psi(c), y, 0, 0.0, 0.0, nullptr));
+            CAL_HIP_OTHER(c, launch_dot(y, P.psi(c), 2 * P.n, part, nd, c->stream));
+            CAL_HIP_OTHER(c, launch_reduce(part, nd, 1, c->d_red + 1 + nq, c->stream));
+        }
+    }
+    double* h = P.h_coef + 2 * kPropMaxCols;
+    CAL_HIP_OTHER(c, hipMemcpyAsync(h, c->d_red, (size_t)(nq + (P.energy ? 2 : 1)) * sizeof(double),
+                                    hipMemcpyDeviceToHost, c->stream));
     CAL_HIP(c, hipStreamSynchronize(c->stream));
-    P.nrm2 = P.h_coef[2 * kPropMaxCols];
+    P.nrm2 = h[0];
     return 0;
+}
+
+// the history row of the step just completed (combine_dev's transfer is in h_coef)
+void record_row(PropState& P) {
+    const double* h = P.h_coef + 2 * kPropMaxCols;
+    const int nq = P.nq();
+    P.hist.push_back(P.t);
+    P.hist.push_back(h[0]);
+    P.hist.push_back(P.energy ? h[1 + nq] : std::numeric_limits<double>::quiet_NaN());
+    P.hist.insert(P.hist.end(), h + 1, h + 1 + nq);
 }
 
 // One Krylov build from the current state: CA blocks until max_blocks, the
@@ -224,6 +298,123 @@ int cal_prop_combine(cal_ctx* c, int64_t n, int m, const double* Q, const double
     return 0;
 }
 
+// W, phi_re and phi_im (null: zeros) as columns of ldo doubles at dst, on the stream
+static int upload_obs(cal_ctx* c, double* dst, int64_t ldo, int64_t n, int nw, const double* W, int nphi,
+                      const double* phi_re, const double* phi_im) {
+    const size_t cols = (size_t)nw + 2 * (size_t)nphi;
+    if (cols == 0) return 0;
+    CAL_HIP(c, hipMemsetAsync(dst, 0, cols * ldo * sizeof(double), c->stream));
+    auto put = [&](double* d, const double* src, int k) -> int {
+        if (k > 0 && src)
+            CAL_HIP(c, hipMemcpy2DAsync(d, ldo * sizeof(double), src, n * sizeof(double), n * sizeof(double), k,
+                                        hipMemcpyHostToDevice, c->stream));
+        return 0;
+    };
+    CAL_TRY(put(dst, W, nw));
+    CAL_TRY(put(dst + (size_t)nw * ldo, phi_re, nphi));
+    CAL_TRY(put(dst + (size_t)(nw + nphi) * ldo, phi_im, nphi));
+    return 0;
+}
+
+static bool obs_counts_ok(int nw, const double* W, int nphi, const double* phi_re) {
+    return nw >= 0 && nw <= kPropMaxObs && nphi >= 0 && nphi <= kPropMaxObs && (nw == 0 || W) && (nphi == 0 || phi_re);
+}
+
+int cal_prop_combine_obs(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
+                         int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
+                         double* out_re, double* out_im, double* norm2, double* sums) {
+    if (!c) return CAL_ERR_ARG;
+    hipSetDevice(c->device);
+    if (n < 1 || m < 1 || m > kPropMaxCols || !Q || !c_re || !c_im || !out_re || !out_im)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_combine_obs: need n >= 1, 1 <= m <= 512 and non-null arrays");
+    const int nq = nw + 2 * nphi;
+    if (!obs_counts_ok(nw, W, nphi, phi_re) || (nq > 0 && !sums))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_combine_obs: need 0 <= nw, nphi <= 4 with their arrays and sums");
+    const int64_t ld = ((2 * n + 63) / 64) * 64;
+    const int64_t ldo = ((n + 63) / 64) * 64;
+    const int nb = prop_combine_blocks(n);
+    // Q (ld x m), out (ld), W and phi (ldo x nq), the coefficients (2 m)
+    CAL_TRY(ensure_scratch(c, (size_t)ld * (m + 1) + (size_t)ldo * nq + 2 * (size_t)m));
+    CAL_TRY(ensure_partial(c, (size_t)(1 + nq) * nb));
+    CAL_TRY(ensure_red(c, (size_t)nq + 1));
+    double* dQ = c->d_scratch;
+    double* dout = dQ + (size_t)ld * m;
+    double* dobs = dout + ld;
+    double* dco = dobs + (size_t)ldo * nq;
+    CAL_HIP(c, hipMemcpy2DAsync(dQ, ld * sizeof(double), Q, 2 * n * sizeof(double), 2 * n * sizeof(double), m,
+                                hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco, c_re, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_TRY(upload_obs(c, dobs, ldo, n, nw, W, nphi, phi_re, phi_im));
+    PropObs o;
+    o.W = dobs;
+    o.pr = dobs + (size_t)nw * ldo;
+    o.pi = dobs + (size_t)(nw + nphi) * ldo;
+    o.ld = ldo;
+    o.nw = nw;
+    o.np = nphi;
+    const int t = timer_begin(c, 2, ((double)2 * n * m + (double)2 * n + (double)n * nq) * 8.0);
+    const hipError_t e = launch_prop_combine_obs(dQ, ld, n, m, dco, dco + m, dout, c->d_partial, o, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine_obs");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1 + nq, c->d_red, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out_re, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out_im, dout + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    double red[1 + 3 * kPropMaxObs] = {0.0};
+    CAL_HIP(c, hipMemcpyAsync(red, c->d_red, (size_t)(1 + nq) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    if (norm2) *norm2 = red[0];
+    for (int q = 0; q < nq; ++q) sums[q] = red[1 + q];
+    return 0;
+}
+
+int cal_prop_set_observables(cal_ctx* c, int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
+                             int energy) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_set_observables: no active propagator");
+    hipSetDevice(c->device);
+    PropState& P = *c->prop;
+    if (!obs_counts_ok(nw, W, nphi, phi_re))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_set_observables: need 0 <= nw, nphi <= 4 with their arrays");
+    if (!c->has_A || c->A.n_local != 2 * P.n)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_set_observables: the context's matrix changed since cal_prop_begin");
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    obs_free(P);
+    const int nq = nw + 2 * nphi;
+    if (nq > 0) {
+        P.ldo = ((P.n + 63) / 64) * 64;
+        CAL_HIP(c, hipMalloc((void**)&P.d_obs, (size_t)nq * P.ldo * sizeof(double)));
+        const int st = upload_obs(c, P.d_obs, P.ldo, P.n, nw, W, nphi, phi_re, phi_im);
+        if (st < 0 || hipStreamSynchronize(c->stream) != hipSuccess) {  // the sources are the caller's
+            obs_free(P);
+            return st < 0 ? st : set_error(c, CAL_ERR_HIP, "cal_prop_set_observables: upload failed");
+        }
+    }
+    if (energy) {
+        const int64_t ld = c->A.ld;
+        CAL_HIP(c, hipMalloc((void**)&P.d_hpsi, ld * sizeof(double)));
+        CAL_HIP(c, hipMemsetAsync(P.d_hpsi, 0, ld * sizeof(double), c->stream));
+        P.eparts = spmv_lanczos_parts(c, P.psi(c), nullptr, P.d_hpsi + c->A.lpad);
+    }
+    P.nw = nw;
+    P.nphi = nphi;
+    P.energy = energy != 0;
+    return 0;
+}
+
+int cal_prop_get_observables(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows, int* ncols) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_get_observables: no active propagator");
+    const PropState& P = *c->prop;
+    const int nc = 3 + P.nq();
+    const int64_t nr = (int64_t)(P.hist.size() / nc);
+    if (nrows) *nrows = nr;
+    if (ncols) *ncols = nc;
+    if (!out) return 0;
+    if (first < 0 || count < 0 || first + count > nr)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_get_observables: rows [first, first + count) out of range");
+    std::memcpy(out, P.hist.data() + (size_t)first * nc, (size_t)count * nc * sizeof(double));
+    return 0;
+}
+
 static int prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* psi_im, int s, int max_blocks,
                       const char* basis, const double* eigest, int neig) {
     bool newton = false;
@@ -255,8 +446,8 @@ static int prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double*
     const int64_t ld = c->A.ld;
     CAL_HIP(c, hipMalloc((void**)&P->d_psi, ld * sizeof(double)));
     CAL_HIP(c, hipMalloc((void**)&P->d_coef, 2 * kPropMaxCols * sizeof(double)));
-    CAL_HIP(c, hipHostMalloc((void**)&P->h_coef, (2 * kPropMaxCols + 8) * sizeof(double), hipHostMallocDefault));
-    std::memset(P->h_coef, 0, (2 * kPropMaxCols + 8) * sizeof(double));
+    CAL_HIP(c, hipHostMalloc((void**)&P->h_coef, (2 * kPropMaxCols + 16) * sizeof(double), hipHostMallocDefault));
+    std::memset(P->h_coef, 0, (2 * kPropMaxCols + 16) * sizeof(double));
     CAL_HIP(c, hipMemsetAsync(P->d_psi, 0, ld * sizeof(double), c->stream));
     CAL_HIP(c, hipMemcpyAsync(P->psi(c), psi_re, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (psi_im)
@@ -313,6 +504,8 @@ int cal_prop_step(cal_ctx* c, double dt, double tol, int adaptive, int nsteps) {
         const LanczosView v = lanczos_view(c);
         status = combine_dev(c, P, v.Q, v.ld, ks, cre.data(), cim.data());
         if (status < 0) break;
+        P.t += dt;
+        if (P.obs_on()) record_row(P);
         P.info.steps++;
         P.info.lsteps = ks;
         P.info.lsteps_max = std::max(P.info.lsteps_max, ks);

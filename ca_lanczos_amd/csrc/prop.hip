@@ -21,6 +21,22 @@
 // row order top then bottom, pair by pair; wave tree; the four waves in
 // order): launch_reduce turns them into the next step's squared norm without
 // another sweep, deterministically (no atomics).
+//
+// OBS = true (launch_prop_combine_obs) also reduces observables of the new
+// state in the same sweep: nw real diagonal operators W_k and np reference
+// states phi_r = pr + i pi, each streamed once (a lane's two adjacent rows
+// with one 16-byte load: the library's own aligned allocation with an even
+// leading dimension).  Per output row, t = Re psi'[i], b = Im psi'[i]:
+//   W_k  :  d = t*t;  d = d + b*b;  accW[k] = accW[k] + w*d
+//   phi_r:  accRe[r] = accRe[r] + pr*t;  accRe[r] = accRe[r] + pi*b
+//           accIm[r] = accIm[r] + pr*b;  accIm[r] = accIm[r] - pi*t
+// a lane's rows in row order, pair by pair (the nrm chain's order), then the
+// nrm chain's wave tree and wave order.  Quantity q's block partial goes to
+// partial[q * gridDim.x + block] (launch_reduce's entry-major layout): q = 0
+// the squared norm, 1 + k <W_k>, 1 + nw + 2r / + 2r + 1 Re / Im <phi_r|psi'>.
+// The counts are kernel arguments; the loops over them are unrolled to the
+// cap with wave-uniform guards, so every accumulator is a register.  The nrm
+// chain and the stores are those of OBS = false: same state, same norm bits.
 #include "cal_internal.hpp"
 
 namespace cal {
@@ -64,15 +80,84 @@ __device__ __forceinline__ void store2(double* __restrict__ p, double x0, double
     }
 }
 
-template <bool VT, bool VB>
+// the OBS kernel's extra argument; OBS = false carries an empty one
+template <bool OBS>
+struct PropObsArg {};
+template <>
+struct PropObsArg<true> {
+    PropObs o;
+};
+
+struct PropObsAcc {
+    double w[kPropMaxObs], re[kPropMaxObs], im[kPropMaxObs];
+};
+
+// the observables' wave sums (LDS of the OBS kernels only)
+__device__ __forceinline__ double (*obs_wave_sums())[kPropThreads / 64] {
+    __shared__ double wo[3 * kPropMaxObs][kPropThreads / 64];
+    return wo;
+}
+
+// the observables' terms of the adjacent rows r, r + 1 (PAIR) or of row r alone
+template <bool PAIR>
+__device__ __forceinline__ void obs_rows(const PropObs& o, int64_t r, double t0, double t1, double b0, double b1,
+                                         PropObsAcc& s) {
+#pragma unroll
+    for (int k = 0; k < kPropMaxObs; ++k)
+        if (k < o.nw) {
+            const double* w = o.W + k * o.ld + r;
+            double w0, w1 = 0.0;
+            if (PAIR) load2<true>(w, w0, w1);
+            else w0 = *w;
+            double d = t0 * t0;
+            d = d + b0 * b0;
+            s.w[k] = s.w[k] + w0 * d;
+            if (PAIR) {
+                d = t1 * t1;
+                d = d + b1 * b1;
+                s.w[k] = s.w[k] + w1 * d;
+            }
+        }
+#pragma unroll
+    for (int k = 0; k < kPropMaxObs; ++k)
+        if (k < o.np) {
+            const double* pr = o.pr + k * o.ld + r;
+            const double* pi = o.pi + k * o.ld + r;
+            double r0, r1 = 0.0, i0, i1 = 0.0;
+            if (PAIR) {
+                load2<true>(pr, r0, r1);
+                load2<true>(pi, i0, i1);
+            } else {
+                r0 = *pr;
+                i0 = *pi;
+            }
+            s.re[k] = s.re[k] + r0 * t0;
+            s.re[k] = s.re[k] + i0 * b0;
+            s.im[k] = s.im[k] + r0 * b0;
+            s.im[k] = s.im[k] - i0 * t0;
+            if (PAIR) {
+                s.re[k] = s.re[k] + r1 * t1;
+                s.re[k] = s.re[k] + i1 * b1;
+                s.im[k] = s.im[k] + r1 * b1;
+                s.im[k] = s.im[k] - i1 * t1;
+            }
+        }
+}
+
+template <bool VT, bool VB, bool OBS>
 __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __restrict__ Q, int64_t ld, int64_t n,
                                                                int m, const double* __restrict__ a,
                                                                const double* __restrict__ b,
                                                                double* __restrict__ out,
-                                                               double* __restrict__ partial) {
+                                                               double* __restrict__ partial, PropObsArg<OBS> obs) {
     __shared__ double sa[kPropMaxCols];
     __shared__ double sb[kPropMaxCols];
     __shared__ double ws[kPropThreads / 64];
+    PropObsAcc acc;
+    if constexpr (OBS) {
+#pragma unroll
+        for (int k = 0; k < kPropMaxObs; ++k) acc.w[k] = acc.re[k] = acc.im[k] = 0.0;
+    }
     for (int j = threadIdx.x; j < m; j += kPropThreads) {
         sa[j] = a[j];
         sb[j] = b[j];
@@ -111,6 +196,7 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
             nrm = nrm + t1 * t1;
             nrm = nrm + b0 * b0;
             nrm = nrm + b1 * b1;
+            if constexpr (OBS) obs_rows<true>(obs.o, r, t0, t1, b0, b1, acc);
         } else if (r < n) {  // the last row of an odd n
             const double* qt = Q + r;
             const double* qb = Q + n + r;
@@ -129,13 +215,40 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
             out[n + r] = b0;
             nrm = nrm + t0 * t0;
             nrm = nrm + b0 * b0;
+            if constexpr (OBS) obs_rows<false>(obs.o, r, t0, 0.0, b0, 0.0, acc);
         }
     }
     nrm = prop_wave_sum(nrm);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) ws[wave] = nrm;
+    if constexpr (OBS) {
+        double(*wo)[kPropThreads / 64] = obs_wave_sums();
+        const int nw = obs.o.nw, np = obs.o.np;
+#pragma unroll
+        for (int k = 0; k < kPropMaxObs; ++k)
+            if (k < nw) {
+                const double v = prop_wave_sum(acc.w[k]);
+                if (lane == 0) wo[k][wave] = v;
+            }
+#pragma unroll
+        for (int k = 0; k < kPropMaxObs; ++k)
+            if (k < np) {
+                const double vr = prop_wave_sum(acc.re[k]);
+                const double vi = prop_wave_sum(acc.im[k]);
+                if (lane == 0) {
+                    wo[nw + 2 * k][wave] = vr;
+                    wo[nw + 2 * k + 1][wave] = vi;
+                }
+            }
+    }
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+    if constexpr (OBS) {  // thread q writes quantity q of this block
+        double(*wo)[kPropThreads / 64] = obs_wave_sums();
+        const int q = (int)threadIdx.x - 1;
+        if (q >= 0 && q < obs.o.nw + 2 * obs.o.np)
+            partial[(int64_t)(q + 1) * gridDim.x + blockIdx.x] = ((wo[q][0] + wo[q][1]) + wo[q][2]) + wo[q][3];
+    }
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -147,8 +260,9 @@ int prop_combine_blocks(int64_t n) {
     return (int)(b < 1 ? 1 : b);
 }
 
-hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                               double* out, double* partial, hipStream_t st) {
+template <bool OBS>
+static hipError_t launch_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
+                                 double* out, double* partial, PropObsArg<OBS> obs, hipStream_t st) {
     if (n < 1 || m < 1 || m > kPropMaxCols || ld < 2 * n) return hipErrorInvalidValue;
     if (n > ((int64_t)1 << 40)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)prop_combine_blocks(n)), block(kPropThreads);
@@ -158,14 +272,33 @@ hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, co
     const bool vt = even && aligned16(Q) && aligned16(out);
     const bool vb = even && aligned16(Q + n) && aligned16(out + n);
     if (vt && vb)
-        hipLaunchKernelGGL((k_prop_combine<true, true>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial);
+        hipLaunchKernelGGL((k_prop_combine<true, true, OBS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
     else if (vt)
-        hipLaunchKernelGGL((k_prop_combine<true, false>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial);
+        hipLaunchKernelGGL((k_prop_combine<true, false, OBS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
     else if (vb)
-        hipLaunchKernelGGL((k_prop_combine<false, true>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial);
+        hipLaunchKernelGGL((k_prop_combine<false, true, OBS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
     else
-        hipLaunchKernelGGL((k_prop_combine<false, false>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial);
+        hipLaunchKernelGGL((k_prop_combine<false, false, OBS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial,
+                           obs);
     return hipGetLastError();
+}
+
+hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
+                               double* out, double* partial, hipStream_t st) {
+    return launch_combine<false>(Q, ld, n, m, a, b, out, partial, PropObsArg<false>{}, st);
+}
+
+hipError_t launch_prop_combine_obs(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
+                                   double* out, double* partial, const PropObs& o, hipStream_t st) {
+    if (o.nw < 0 || o.nw > kPropMaxObs || o.np < 0 || o.np > kPropMaxObs) return hipErrorInvalidValue;
+    if ((o.nw > 0 && !o.W) || (o.np > 0 && (!o.pr || !o.pi))) return hipErrorInvalidValue;
+    // the observables' 16-byte loads: aligned origins, an even leading dimension of at least n rows
+    if (o.nw + o.np > 0 && (o.ld < n || (o.ld & 1) != 0)) return hipErrorInvalidValue;
+    if ((o.nw > 0 && !aligned16(o.W)) || (o.np > 0 && (!aligned16(o.pr) || !aligned16(o.pi))))
+        return hipErrorInvalidValue;
+    PropObsArg<true> arg;
+    arg.o = o;
+    return launch_combine<true>(Q, ld, n, m, a, b, out, partial, arg, st);
 }
 
 }  // namespace cal

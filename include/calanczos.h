@@ -352,6 +352,27 @@ int cal_prop_step(cal_ctx* ctx, double dt, double tol, int adaptive, int nsteps)
 int cal_prop_get(cal_ctx* ctx, double* psi_re, double* psi_im, cal_prop_info* info);
 int cal_prop_end(cal_ctx* ctx);
 
+/* Observables of the state after each later time step, reduced on the device inside the combine sweep.
+ * W: n x nw column-major real diagonal operators (0 <= nw <= 4; NULL when nw = 0).  phi_re / phi_im: n x nphi
+ * reference states (0 <= nphi <= 4; phi_im may be NULL = real).  energy != 0 also records <psi|H|psi> (one more SpMV
+ * per step).  Replaces an earlier set and clears the history; nw = nphi = energy = 0 switches them off.
+ * CAL_ERR_ARG without an active propagator or outside the caps. */
+int cal_prop_set_observables(cal_ctx* ctx, int nw, const double* W, int nphi, const double* phi_re,
+                             const double* phi_im, int energy);
+/* Row k (one per completed step since the set): [t, norm2, energy (NaN when off), <W_0>..<W_{nw-1}>,
+ * Re<phi_0|psi>, Im<phi_0|psi>, ...], t the time since cal_prop_begin, <W_k> = sum W_k |psi|^2, <phi|psi> =
+ * sum conj(phi) psi.  A step that ends in CAL_WARN_BREAKDOWN records no row.  out == NULL: only *nrows / *ncols.
+ * Copies rows [first, first+count), row-major with *ncols = 3 + nw + 2 nphi doubles each. */
+int cal_prop_get_observables(cal_ctx* ctx, int64_t first, int64_t count, double* out, int64_t* nrows, int* ncols);
+/* The OBS kernel on host data, as cal_prop_combine is for the plain one: same out / norm2 (to the bit), plus
+ * sums[nw + 2 nphi] in the order of a history row's last columns.  Per output row, t = out_re[i], b = out_im[i]:
+ *   W_k  :  d = t*t;  d = d + b*b;  acc = acc + W_k[i]*d
+ *   phi_r:  re = re + pr[i]*t;  re = re + pi[i]*b;  im = im + pr[i]*b;  im = im - pi[i]*t
+ * summed over the rows in the squared norm's fixed order. */
+int cal_prop_combine_obs(cal_ctx* ctx, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
+                         int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
+                         double* out_re, double* out_im, double* norm2, double* sums);
+
 /* [T,Q,lsteps] = ca_lanczos_prop(A,r0,s,m,dt,tol,basis,eigest,adaptive)
  * (ca_lanczos_prop.m:3-135) with r0 = r_re + i r_im (r_im may be NULL) on the
  * stacked matrix: T is *lsteps x *lsteps (ld *lsteps; room for s*m squared),
