@@ -20,6 +20,7 @@ from .api import (  # noqa: F401
     compute_ritz_rnorm,
     context_for,
     default_context,
+    drive_rows,
     eig,
     expm_col1,
     lanczos,

@@ -225,6 +225,29 @@ class Context:
         ov = sums[nw:nw + 2 * nphi]
         return ore + 1j * oim, n2.value, sums[:nw].copy(), ov[0::2] + 1j * ov[1::2]
 
+    def set_diagonal(self, d):
+        """Rewrite the stored diagonal of the resident matrix in place
+        (cal_set_diagonal): one entry per row, no new upload or analysis.
+        Needs a "csr" or "split" matrix with exactly one stored diagonal
+        entry in every row; refused (CalError, nothing written) otherwise,
+        while a Lanczos run or a propagator is open, and on a context handed
+        out by ``context_for(A)`` -- that cache pairs the device copy with
+        the SciPy object, so ``set_diagonal`` wants an explicit ``Context``."""
+        if getattr(self, "_cached_for_matrix", False):
+            raise CalError(_lib.CAL_ERR_ARG, "set_diagonal: this context is the cached device copy of a SciPy matrix "
+                                             "(context_for); set_diagonal wants an explicit Context")
+        d = np.ascontiguousarray(d, dtype=np.float64).ravel()
+        check(self.h, lib.cal_set_diagonal(self.h, d.shape[0], ptr(d)), "set_diagonal")
+        return self
+
+    def get_diagonal(self):
+        """The stored diagonal of the resident matrix (cal_get_diagonal;
+        the 2n entries of blkdiag(H, H) while a propagator is open)."""
+        n = self.matrix_info()["n_local"]
+        d = np.zeros(n)
+        check(self.h, lib.cal_get_diagonal(self.h, n, ptr(d)), "get_diagonal")
+        return d
+
     def set_matrix_csc(self, A):
         """MATLAB's sparse storage (mxGetJc / mxGetIr / mxGetPr: CSC with int64
         mwIndex arrays) through cal_set_matrix_csc, the entry a MEX shim uses."""
@@ -462,6 +485,7 @@ def context_for(A) -> Context:
     if hit is not None:  # a dead matrix's id, reused before its callback ran
         _evict(key, hit[0])
     ctx = Context().set_matrix(A)
+    ctx._cached_for_matrix = True  # Context.set_diagonal refuses: the cache pairs the device copy with A
     try:
         ref = weakref.ref(A, lambda r, key=key: _evict(key, r))
     except TypeError:  # pragma: no cover  (not weak-referenceable: kept for the process)
@@ -873,6 +897,40 @@ def _obs_arrays(n, W, phi):
     return Wm, f64(p.real), f64(p.imag)
 
 
+def drive_rows(drive, t0, dt, nsteps, scheme="midpoint"):
+    """The amplitude rows ``Propagator.step`` hands to cal_prop_step_driven
+    and the size of the (sub-)step each row is taken with: (rows (nrows x nk,
+    C order), sub).  An array drive is taken as it is (nsteps rows, sub = dt);
+    a callable is sampled by the scheme (see ``Propagator.step``)."""
+    if not callable(drive):
+        rows = np.ascontiguousarray(np.asarray(drive, dtype=np.float64))
+        if rows.ndim == 1:
+            rows = rows.reshape(nsteps, -1)
+        if rows.ndim != 2 or rows.shape[0] != nsteps:
+            raise ValueError("drive needs one row of amplitudes per step")
+        return rows, dt
+
+    def f(t):
+        return np.atleast_1d(np.asarray(drive(t), dtype=np.float64)).ravel()
+    if scheme == "midpoint":
+        rows = [f(t0 + j * dt + 0.5 * dt) for j in range(nsteps)]
+        sub = dt
+    elif scheme == "cf4":
+        r3 = math.sqrt(3.0)
+        a1, a2 = 0.5 + r3 / 3.0, 0.5 - r3 / 3.0
+        rows = []
+        for j in range(nsteps):
+            f1 = f(t0 + j * dt + (0.5 - r3 / 6.0) * dt)
+            f2 = f(t0 + j * dt + (0.5 + r3 / 6.0) * dt)
+            rows.append(a1 * f1 + a2 * f2)  # the right factor acts first
+            rows.append(a2 * f1 + a1 * f2)
+        sub = 0.5 * dt
+    else:
+        raise ValueError("scheme must be \"midpoint\" or \"cf4\"")
+    nk = len(rows[0]) if rows else 0
+    return np.ascontiguousarray(np.array(rows, dtype=np.float64).reshape(len(rows), nk)), sub
+
+
 class Propagator:
     """Time stepper ``psi <- exp(-i dt H) psi`` for a real symmetric sparse H
     and a complex state (cal_prop_*; ca_lanczos_prop.m as runLanczos.m:84-131
@@ -883,6 +941,8 @@ class Propagator:
     def __init__(self, H, psi0, s, max_blocks, basis="newton", eigest=None, ctx=None):
         self.n = H.shape[0]
         self._nw = 0
+        self._nk = 0
+        self.t = 0.0  # the propagator's clock: the sum of the (sub-)steps taken through step()
         self._own = ctx is None
         self.ctx = ctx or Context()
         try:
@@ -899,11 +959,56 @@ class Propagator:
             raise
         self._open = True
 
-    def step(self, dt, nsteps=1, tol=1.0e-10, adaptive=False):
+    def step(self, dt, nsteps=1, tol=1.0e-10, adaptive=False, drive=None, scheme="midpoint"):
         """nsteps time steps of size dt; returns the status (0, or
-        CAL_WARN_BREAKDOWN when a step's first block broke down)."""
-        return check(self.ctx.h, lib.cal_prop_step(self.ctx.h, float(dt), float(tol), 1 if adaptive else 0,
-                                                   int(nsteps)), "prop_step")
+        CAL_WARN_BREAKDOWN when a step's first block broke down).
+
+        ``drive`` (after ``set_drive``) steps under H(t) = H0 + sum_k f_k(t)
+        diag(W_k).  An array (nsteps, nk) is used row by row, one row of
+        amplitudes per step.  A callable ``t -> nk amplitudes`` is sampled by
+        ``scheme``: "midpoint" takes ``drive(t_j + dt/2)`` for step j (the
+        exponential midpoint rule, second order); "cf4" is the commutator-free
+        fourth-order rule, two sub-steps of dt/2 per step,
+        ``exp(-i dt/2 (a2 A1 + a1 A2)) exp(-i dt/2 (a1 A1 + a2 A2))`` (right
+        factor first) with ``A_i = H(t_j + (1/2 -+ sqrt(3)/6) dt)`` and
+        ``a_{1,2} = 1/2 +- sqrt(3)/3`` -- two rows of amplitudes (and two
+        history rows of the observables) per step through the same call.
+        ``self.t`` advances by the sub-steps' sum.  ``drive=None`` is the
+        undriven call: it steps under whatever H the last driven step left."""
+        if drive is None:
+            st = check(self.ctx.h, lib.cal_prop_step(self.ctx.h, float(dt), float(tol), 1 if adaptive else 0,
+                                                     int(nsteps)), "prop_step")
+            self.t += float(dt) * int(nsteps)
+            return st
+        rows, sub = drive_rows(drive, self.t, float(dt), int(nsteps), scheme)
+        if rows.shape[1] != self._nk:
+            raise ValueError("drive has %d amplitudes per step, set_drive has %d operators" % (rows.shape[1], self._nk))
+        st = check(self.ctx.h, lib.cal_prop_step_driven(self.ctx.h, sub, float(tol), 1 if adaptive else 0,
+                                                        rows.shape[0], ptr(rows), max(rows.shape[1], 1)),
+                   "prop_step_driven")
+        self.t += sub * rows.shape[0]
+        return st
+
+    def set_drive(self, W):
+        """The operators of the drive H(t) = H0 + sum_k f_k(t) diag(W_k): real
+        diagonal operators W (a list or n x nk, at most 4), copied to the
+        device; H0 is the matrix as it is now.  ``None`` switches the drive off
+        and restores H0's diagonal, as ``close()`` does.  Needs a "csr" or
+        "split" context (``Context.set_diagonal``'s conditions)."""
+        if not getattr(self, "_open", False):
+            raise CalError(_lib.CAL_ERR_ARG, "set_drive: the propagator is closed")
+        Wm = _obs_arrays(self.n, W, None)[0]
+        nk = Wm.shape[1]
+        check(self.ctx.h, lib.cal_prop_set_drive(self.ctx.h, nk, ptr(Wm) if nk else None), "prop_set_drive")
+        self._nk = nk
+        return self
+
+    def refresh_shifts(self):
+        """Forget the Newton shifts of the first step: the next step computes
+        them from the current H and state (cal_prop_refresh_shifts; for a
+        drive that moves H's spectrum by about its width or more)."""
+        check(self.ctx.h, lib.cal_prop_refresh_shifts(self.ctx.h), "prop_refresh_shifts")
+        return self
 
     def state(self):
         re, im = np.zeros(self.n), np.zeros(self.n)

@@ -233,6 +233,14 @@ struct DevMatrix {
     double* ds_diag = nullptr;       // n + 2 doubles
     double* ds_gsum = nullptr;       // PatArgs::gsum
     double* ds_dprod = nullptr;      // PatArgs::dprod
+    // The stored diagonal's positions (runtime.cpp diag_positions; built at the
+    // first cal_set_diagonal / cal_prop_set_drive, never at upload): val[dpos[r]]
+    // is the entry of row r with col == r.  dpos_state: 0 not looked for, 1
+    // every row has exactly one, -1 a row has none / more than one (the counts
+    // in dpos_missing / dpos_dup; dpos is then not to be used)
+    int* dpos = nullptr;
+    int dpos_state = 0;
+    int64_t dpos_missing = 0, dpos_dup = 0;
     // halo plan (distributed); ghost entries grouped by owning peer
     std::vector<int> peers;              // neighbour ranks
     std::vector<int64_t> recv_off;       // ghost destination per peer, relative to the local origin
@@ -537,12 +545,39 @@ struct PropObs {
 hipError_t launch_prop_combine_obs(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
                                    double* out, double* partial, const PropObs& o, hipStream_t st);
 
+// ---- the time-dependent diagonal H(t) = H0 + sum_k f_k(t) diag(W_k) (prop.hip) ----
+// k_diag_find: dpos[r] = the position in val of row r's first entry with
+// col == r (-1: none), r < n; partial[block] = the block's rows without such
+// an entry, partial[blocks + block] = its rows with more than one (exact
+// small integers as doubles; blocks = diag_find_blocks(n);
+// launch_reduce(partial, blocks, 2, ...) sums both).
+int diag_find_blocks(int64_t n);
+hipError_t launch_diag_find(const int* rowptr, const int* col, int64_t n, int* dpos, double* partial, hipStream_t st);
+// k_diag_drive: for i < n
+//   d = V0[i];  for k = 0 .. nk-1 (ascending):  p = f[k] * W[i + k ldw];  d = d + p
+// (product and sum round separately), then val[dpos[i + h n]] = d and, with
+// ds_diag non-null, ds_diag[i + h n] = d for h < halves (1 or 2).  nk <=
+// kDriveMaxOps; every dpos entry must be a valid position (dpos_state == 1).
+constexpr int kDriveMaxOps = 4;
+struct DiagDrive {
+    const double* V0 = nullptr;
+    const double* W = nullptr;
+    int64_t ldw = 0, n = 0;
+    int nk = 0, halves = 1;
+    double f[kDriveMaxOps] = {};
+    const int* dpos = nullptr;
+    double* val = nullptr;
+    double* ds_diag = nullptr;
+};
+hipError_t launch_diag_drive(const DiagDrive& a, hipStream_t st);
+
 
 }  // namespace cal
 
 // Per-launch kernel timer (HIP events on the launching stream).
 struct CalTimerRec {
-    int kind;  // 0 spmv, 1 gram, 2 apply, 3 other, 4 allreduce (RCCL), 5 halo exchange (RCCL)
+    int kind;  // 0 spmv, 1 gram, 2 apply, 3 other, 4 allreduce (RCCL), 5 halo exchange (RCCL), 6 normest,
+               // 7 drive (k_diag_drive: the diagonal rewritten by cal_set_diagonal / a driven time step)
     hipEvent_t a, b;
     double bytes;  // the launch's algorithmic HBM bytes, 0 if not stated
 };
@@ -842,6 +877,20 @@ int spmv_lanczos_dev(cal_ctx* c, const double* x, const double* xprev, const dou
 // y = A x (mode 0, or 3 on CSR) on stream st without timers or statistics
 // (one rank; the asynchronous normest)
 hipError_t spmv_on_stream(const cal_ctx* c, const double* x, double* y, int mode, const double* xnrm, hipStream_t st);
+// The stored diagonal as a device vector (runtime.cpp).  Supported: one rank,
+// a whole single slab, the matrix on CSR or on the diagonal-split format, and
+// exactly one stored diagonal entry in every row; anything else is
+// CAL_ERR_UNSUPPORTED with the cause in the message and nothing written.
+// diag_positions: finds the positions once per uploaded matrix (one host wait
+// for the two counts) and answers from the cached verdict afterwards.
+int diag_positions(cal_ctx* c);
+// H's diagonal <- V0 + sum_k f[k] W(:, k) (launch_diag_drive; V0 / W on the
+// device, f on the host; n = n_local / halves) into val and, on the split
+// format, ds_diag; enqueued on the stream, no host wait once the positions exist
+int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
+                    const double* f);
+// dst[i] = val[dpos[i]], i < cnt <= n_local (device dst; enqueued)
+int diag_gather_dev(cal_ctx* c, double* dst, int64_t cnt);
 int allreduce_sum(cal_ctx* c, double* d_buf, int64_t count);
 // d_recv[p * count + i] = rank p's d_send[i] (in rank order, every rank)
 int allgather(cal_ctx* c, const double* d_send, double* d_recv, int64_t count);

@@ -14,6 +14,10 @@
 // The state, Q and the norm stay on the device across steps; the Lanczos
 // run's Q / V allocation is reused, and the Newton shifts of the first step
 // serve every later one (runLanczos.m:93-96 passes eigest the same way).
+// A time-dependent potential H(t) = H0 + sum_k f_k(t) diag(W_k)
+// (cal_prop_set_drive / cal_prop_step_driven) rewrites the matrix's stored
+// diagonal in place before each step (prop.hip k_diag_drive through
+// runtime.cpp diag_update_dev): the step itself is unchanged.
 // The one deliberate difference from ca_lanczos_prop.m: :78 projects with
 // doreorth = false, the blocks here apply the library's second-pass rule
 // (projectAndNormalize's 'second'), which is at least as orthogonal.
@@ -54,6 +58,15 @@ struct PropState {
     double* d_hpsi = nullptr;    // energy: H psi (one vector column, A.ld doubles)
     int eparts = 0;              // energy: mode 4's partials (0: SpMV + dot)
     std::vector<double> hist;    // one row of 3 + nw + 2 nphi per completed step
+    // the drive H(t) = H0 + sum_k f_k(t) diag(W_k) (cal_prop_set_drive): H0's
+    // diagonal as it stood when the drive was set and the nk operators, both
+    // library-owned; the matrix (generation drv_gen) holds whatever the last
+    // driven step wrote until the drive goes off, which puts V0 back
+    int nk = 0;
+    double* d_v0 = nullptr;      // n doubles (the first half's diagonal)
+    double* d_drv = nullptr;     // W (nk columns of ldd doubles)
+    int64_t ldd = 0;             // roundup(n, 64)
+    uint64_t drv_gen = 0;
     bool obs_on() const { return nw > 0 || nphi > 0 || energy; }
     int nq() const { return nw + 2 * nphi; }
     double* psi(const cal_ctx* c) const { return d_psi + c->A.lpad; }
@@ -75,8 +88,25 @@ void obs_free(PropState& P) {
     P.hist.clear();
 }
 
+// switch the drive off: V0 back into the matrix it was taken from (when that
+// matrix is still the context's), then the copies are freed
+int drive_off(cal_ctx* c, PropState& P) {
+    int st = 0;
+    if (P.d_v0 && c->has_A && c->A_gen == P.drv_gen && c->A.n_local == 2 * P.n) {
+        st = diag_update_dev(c, P.d_v0, P.n, 2, 0, nullptr, 0, nullptr);
+        if (hipStreamSynchronize(c->stream) != hipSuccess && st == 0) st = CAL_ERR_HIP;
+    }
+    if (P.d_v0) hipFree(P.d_v0);
+    if (P.d_drv) hipFree(P.d_drv);
+    P.d_v0 = P.d_drv = nullptr;
+    P.nk = 0;
+    P.ldd = 0;
+    return st;
+}
+
 void prop_free(cal_ctx* c) {
     if (!c || !c->prop) return;
+    drive_off(c, *c->prop);
     obs_free(*c->prop);
     if (c->prop->d_psi) hipFree(c->prop->d_psi);
     if (c->prop->d_coef) hipFree(c->prop->d_coef);
@@ -475,25 +505,44 @@ int cal_prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* ps
     return st;
 }
 
-int cal_prop_step(cal_ctx* c, double dt, double tol, int adaptive, int nsteps) {
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_step: no active propagator");
+// nsteps time steps; f non-null: before step `it` the diagonal is set to
+// V0 + sum_k f[it ldf + k] W_k (one k_diag_drive launch, enqueued ahead of the
+// step's first kernel on the same stream)
+static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int adaptive, int nsteps, const double* f,
+                      int ldf) {
+    const std::string w = who;
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, w + ": no active propagator");
     hipSetDevice(c->device);
     PropState& P = *c->prop;
     if (!std::isfinite(dt) || nsteps < 0 || std::isnan(tol))
-        return set_error(c, CAL_ERR_ARG, "cal_prop_step: need a finite dt, a tol and nsteps >= 0");
+        return set_error(c, CAL_ERR_ARG, w + ": need a finite dt, a tol and nsteps >= 0");
     if (!c->has_A || c->A.n_local != 2 * P.n)
-        return set_error(c, CAL_ERR_ARG, "cal_prop_step: the context's matrix changed since cal_prop_begin");
+        return set_error(c, CAL_ERR_ARG, w + ": the context's matrix changed since cal_prop_begin");
+    if (f) {
+        if (P.nk < 1 || !P.d_v0) return set_error(c, CAL_ERR_ARG, w + ": no drive set (cal_prop_set_drive)");
+        if (c->A_gen != P.drv_gen)
+            return set_error(c, CAL_ERR_ARG, w + ": the context's matrix changed since cal_prop_set_drive");
+        if (ldf < P.nk) return set_error(c, CAL_ERR_ARG, w + ": need ldf >= nk");
+        for (int it = 0; it < nsteps; ++it)
+            for (int k = 0; k < P.nk; ++k)
+                if (!std::isfinite(f[(size_t)it * ldf + k]))
+                    return set_error(c, CAL_ERR_ARG, w + ": non-finite amplitude in f");
+    }
     const double t0 = now_ms();
     std::vector<double> cre, cim;
     int status = 0;
     for (int it = 0; it < nsteps; ++it) {
+        if (f) {
+            status = diag_update_dev(c, P.d_v0, P.n, 2, P.nk, P.d_drv, P.ldd, f + (size_t)it * ldf);
+            if (status < 0) break;
+        }
         const double nrm = std::sqrt(P.nrm2);
         int kuse = 0;
         double resid = 0.0;
         status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid);
         if (status < 0) break;
         if (kuse == 0) {  // the state is unchanged
-            status = set_error(c, CAL_WARN_BREAKDOWN, "cal_prop_step: the first CA block broke down");
+            status = set_error(c, CAL_WARN_BREAKDOWN, w + ": the first CA block broke down");
             break;
         }
         const int ks = kuse * P.s;
@@ -516,6 +565,61 @@ int cal_prop_step(cal_ctx* c, double dt, double tol, int adaptive, int nsteps) {
     }
     P.info.ms += now_ms() - t0;
     return status;
+}
+
+int cal_prop_step(cal_ctx* c, double dt, double tol, int adaptive, int nsteps) {
+    return prop_steps(c, "cal_prop_step", dt, tol, adaptive, nsteps, nullptr, 0);
+}
+
+int cal_prop_step_driven(cal_ctx* c, double dt, double tol, int adaptive, int nsteps, const double* f, int ldf) {
+    if (!c) return CAL_ERR_ARG;
+    if (!f && nsteps > 0) return set_error(c, CAL_ERR_ARG, "cal_prop_step_driven: need f (nsteps rows of ldf)");
+    return prop_steps(c, "cal_prop_step_driven", dt, tol, adaptive, nsteps, f, ldf);
+}
+
+int cal_prop_set_drive(cal_ctx* c, int nk, const double* W) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: no active propagator");
+    hipSetDevice(c->device);
+    PropState& P = *c->prop;
+    if (nk < 0 || nk > kDriveMaxOps || (nk > 0 && !W))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: need 0 <= nk <= 4 and W (n x nk) when nk > 0");
+    if (!c->has_A || c->A.n_local != 2 * P.n)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: the context's matrix changed since cal_prop_begin");
+    for (size_t i = 0; i < (size_t)nk * P.n; ++i)
+        if (!std::isfinite(W[i])) return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: non-finite entry in W");
+    CAL_TRY(diag_positions(c));  // refusals leave the matrix and an earlier drive as they are
+    CAL_TRY(drive_off(c, P));    // an earlier drive: its V0 goes back first
+    if (nk == 0) return 0;
+    P.ldd = ((P.n + 63) / 64) * 64;
+    P.drv_gen = c->A_gen;
+    CAL_HIP(c, hipMalloc((void**)&P.d_v0, P.n * sizeof(double)));
+    CAL_HIP(c, hipMalloc((void**)&P.d_drv, (size_t)nk * P.ldd * sizeof(double)));
+    int st = diag_gather_dev(c, P.d_v0, P.n);
+    if (st == 0 && hipMemsetAsync(P.d_drv, 0, (size_t)nk * P.ldd * sizeof(double), c->stream) != hipSuccess)
+        st = set_error(c, CAL_ERR_HIP, "cal_prop_set_drive: memset failed");
+    if (st == 0 && hipMemcpy2DAsync(P.d_drv, P.ldd * sizeof(double), W, P.n * sizeof(double), P.n * sizeof(double), nk,
+                                    hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        st = set_error(c, CAL_ERR_HIP, "cal_prop_set_drive: upload failed");
+    if (st == 0 && hipStreamSynchronize(c->stream) != hipSuccess)  // W is the caller's
+        st = set_error(c, CAL_ERR_HIP, "cal_prop_set_drive: upload failed");
+    if (st < 0) {  // nothing was written to the matrix yet
+        hipFree(P.d_v0);
+        hipFree(P.d_drv);
+        P.d_v0 = P.d_drv = nullptr;
+        P.ldd = 0;
+        return st;
+    }
+    P.nk = nk;
+    return 0;
+}
+
+int cal_prop_refresh_shifts(cal_ctx* c) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_refresh_shifts: no active propagator");
+    PropState& P = *c->prop;
+    if (!P.newton) return 0;
+    P.have_shifts = false;
+    P.shifts.clear();
+    return 0;
 }
 
 int cal_prop_get(cal_ctx* c, double* psi_re, double* psi_im, cal_prop_info* info) {

@@ -301,4 +301,103 @@ hipError_t launch_prop_combine_obs(const double* Q, int64_t ld, int64_t n, int m
     return launch_combine<true>(Q, ld, n, m, a, b, out, partial, arg, st);
 }
 
+// ---- the time-dependent diagonal ---------------------------------------------------
+// H(t) = H0 + sum_k f_k(t) diag(W_k) rewrites one stored entry per row: the
+// slot of val with col == row (and the split format's streamed diagonal).
+//
+// k_diag_find (once per matrix) looks that slot up: one row per thread in a
+// grid-stride loop, a plain scan of the row -- empty rows and rows longer
+// than a CSR row block included -- keeping the first hit and counting the
+// hits.  Rows with no hit and rows with several are counted per block (exact
+// small integers in doubles; wave tree, the four waves in order) so that
+// launch_reduce gives the two totals in the fixed order, no atomics.
+//
+// k_diag_drive (once per time step) is one row per lane with 8-byte accesses:
+//   d = V0[i];  k ascending:  p = f_k * W_k[i];  d = d + p
+// product and sum rounded separately (-ffp-contract=off), the amplitudes
+// kernel arguments (wave-uniform) and the loop unrolled to the cap with
+// uniform guards, as the OBS combine's; then the same d goes to the row's
+// slot of either half.  Vector stores only.
+namespace {
+
+constexpr int kDiagThreads = 256;
+
+__global__ __launch_bounds__(kDiagThreads) void k_diag_find(const int* __restrict__ rowptr,
+                                                            const int* __restrict__ col, int64_t n,
+                                                            int* __restrict__ dpos, double* __restrict__ partial) {
+    __shared__ double wm[kDiagThreads / 64];
+    __shared__ double wd[kDiagThreads / 64];
+    double miss = 0.0, dup = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * kDiagThreads;
+    for (int64_t r = (int64_t)blockIdx.x * kDiagThreads + threadIdx.x; r < n; r += stride) {
+        const int p0 = rowptr[r], p1 = rowptr[r + 1];
+        int pos = -1, hits = 0;
+        for (int p = p0; p < p1; ++p)
+            if (col[p] == (int)r) {
+                if (hits == 0) pos = p;
+                ++hits;
+            }
+        dpos[r] = pos;
+        if (hits == 0) miss = miss + 1.0;
+        if (hits > 1) dup = dup + 1.0;
+    }
+    miss = prop_wave_sum(miss);
+    dup = prop_wave_sum(dup);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        wm[wave] = miss;
+        wd[wave] = dup;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = ((wm[0] + wm[1]) + wm[2]) + wm[3];
+        partial[gridDim.x + blockIdx.x] = ((wd[0] + wd[1]) + wd[2]) + wd[3];
+    }
+}
+
+template <bool SPLIT>
+__global__ __launch_bounds__(kDiagThreads) void k_diag_drive(DiagDrive a) {
+    const int64_t i = (int64_t)blockIdx.x * kDiagThreads + threadIdx.x;
+    if (i >= a.n) return;
+    double d = a.V0[i];
+#pragma unroll
+    for (int k = 0; k < kDriveMaxOps; ++k)
+        if (k < a.nk) {
+            const double p = a.f[k] * a.W[k * a.ldw + i];
+            d = d + p;
+        }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (h < a.halves) {
+            const int64_t r = i + h * a.n;
+            a.val[a.dpos[r]] = d;
+            if (SPLIT) a.ds_diag[r] = d;
+        }
+}
+
+}  // namespace
+
+int diag_find_blocks(int64_t n) {
+    int64_t b = (n + kDiagThreads - 1) / kDiagThreads;
+    if (b > 1024) b = 1024;
+    return (int)(b < 1 ? 1 : b);
+}
+
+hipError_t launch_diag_find(const int* rowptr, const int* col, int64_t n, int* dpos, double* partial, hipStream_t st) {
+    if (n < 1 || n >= ((int64_t)1 << 31) || !rowptr || !col || !dpos || !partial) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_diag_find, dim3((unsigned)diag_find_blocks(n)), dim3(kDiagThreads), 0, st, rowptr, col, n,
+                       dpos, partial);
+    return hipGetLastError();
+}
+
+hipError_t launch_diag_drive(const DiagDrive& a, hipStream_t st) {
+    if (a.n < 1 || a.n >= ((int64_t)1 << 31) || a.halves < 1 || a.halves > 2 || a.nk < 0 || a.nk > kDriveMaxOps)
+        return hipErrorInvalidValue;
+    if (!a.V0 || !a.dpos || !a.val || (a.nk > 0 && (!a.W || a.ldw < a.n))) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.n + kDiagThreads - 1) / kDiagThreads)), block(kDiagThreads);
+    if (a.ds_diag) hipLaunchKernelGGL(k_diag_drive<true>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_diag_drive<false>, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
 }  // namespace cal

@@ -210,6 +210,7 @@ static void free_matrix(cal_ctx* c) {
     if (A.ds_diag) hipFree(A.ds_diag);
     if (A.ds_gsum) hipFree(A.ds_gsum);
     if (A.ds_dprod) hipFree(A.ds_dprod);
+    if (A.dpos) hipFree(A.dpos);
     A = DevMatrix();
     if (c->d_work) hipFree(c->d_work);
     c->d_work = nullptr;
@@ -745,6 +746,95 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
     CAL_HIP(c, hipMemcpy(A.blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
     c->has_A = true;
     c->A_gen++;
+    return 0;
+}
+
+// ---- the stored diagonal as a device vector ---------------------------------
+// (cal_set_diagonal / cal_get_diagonal and the propagator's drive, prop.cpp)
+static int diag_supported(cal_ctx* c, const char* who) {
+    if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    const DevMatrix& A = c->A;
+    const std::string w = who;
+    if (c->comm && c->comm->nranks > 1)
+        return set_error(c, CAL_ERR_UNSUPPORTED, w + ": the diagonal is rewritten on one rank only (the context has a "
+                                                     "communicator of several ranks)");
+    if (A.ext_off != 0 || A.n_rows != A.n_local || A.n_local != A.n_global || A.lpad != 0)
+        return set_error(c, CAL_ERR_UNSUPPORTED, w + ": the diagonal is rewritten on a whole single slab only (this "
+                                                     "matrix is a slab of a distributed or extended matrix)");
+    if (A.use_pat)
+        return set_error(c, CAL_ERR_UNSUPPORTED,
+                         w + ": the matrix is stored in the row-pattern format, whose values live in pattern tables "
+                             "(rewriting them needs a new analysis); select \"csr\" or \"split\" with "
+                             "cal_set_spmv_format before the matrix is set");
+    if (A.n_local < 1) return set_error(c, CAL_ERR_UNSUPPORTED, w + ": the matrix has no rows");
+    return 0;
+}
+
+static int diag_verdict(cal_ctx* c) {
+    const DevMatrix& A = c->A;
+    if (A.dpos_state == 1) return 0;
+    if (A.dpos_missing > 0)
+        return set_error(c, CAL_ERR_UNSUPPORTED,
+                         std::to_string(A.dpos_missing) + " row(s) store no diagonal entry: the diagonal can only be "
+                                                          "rewritten where every row stores one (store explicit zeros)");
+    return set_error(c, CAL_ERR_UNSUPPORTED,
+                     std::to_string(A.dpos_dup) + " row(s) store more than one diagonal entry: the diagonal can only "
+                                                  "be rewritten where every row stores exactly one");
+}
+
+int diag_positions(cal_ctx* c) {
+    CAL_TRY(diag_supported(c, "the diagonal"));
+    DevMatrix& A = c->A;
+    if (A.dpos_state != 0) return diag_verdict(c);
+    const int nb = diag_find_blocks(A.n_local);
+    CAL_TRY(ensure_partial(c, 2 * (size_t)nb));
+    CAL_TRY(ensure_red(c, 2));
+    if (!A.dpos) CAL_HIP(c, hipMalloc((void**)&A.dpos, A.n_local * sizeof(int)));
+    const int t = timer_begin(c, 3, (double)A.n_local * 12.0 + (double)A.nnz * 4.0);
+    const hipError_t e = launch_diag_find(A.rowptr, A.col, A.n_local, A.dpos, c->d_partial, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_diag_find");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 2, c->d_red, c->stream));
+    // the one host wait: nothing is written before the two counts are known
+    CAL_HIP(c, hipMemcpyAsync(c->h_red, c->d_red, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    A.dpos_missing = (int64_t)c->h_red[0];
+    A.dpos_dup = (int64_t)c->h_red[1];
+    A.dpos_state = (A.dpos_missing == 0 && A.dpos_dup == 0) ? 1 : -1;
+    return diag_verdict(c);
+}
+
+int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
+                    const double* f) {
+    CAL_TRY(diag_positions(c));
+    DevMatrix& A = c->A;
+    if (halves < 1 || halves > 2 || n < 1 || n * halves != A.n_local || nk < 0 || nk > kDriveMaxOps || !V0_dev ||
+        (nk > 0 && (!W_dev || !f || ldw < n)))
+        return set_error(c, CAL_ERR_ARG, "diag_update_dev: bad arguments");
+    DiagDrive a;
+    a.V0 = V0_dev;
+    a.W = W_dev;
+    a.ldw = ldw;
+    a.n = n;
+    a.nk = nk;
+    a.halves = halves;
+    for (int k = 0; k < nk; ++k) a.f[k] = f[k];
+    a.dpos = A.dpos;
+    a.val = A.val;
+    a.ds_diag = A.use_dsplit ? A.ds_diag : nullptr;
+    // V0, the nk columns and the positions in; the slots (and the streamed diagonal) out
+    const double bytes = (double)n * (8.0 * (1 + nk) + 4.0 * halves) + (double)n * halves * (A.use_dsplit ? 16.0 : 8.0);
+    const int t = timer_begin(c, 7, bytes);  // a kind of its own: one launch per time step, measured alone
+    const hipError_t e = launch_diag_drive(a, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_diag_drive");
+    return 0;
+}
+
+int diag_gather_dev(cal_ctx* c, double* dst, int64_t cnt) {
+    CAL_TRY(diag_positions(c));
+    if (!dst || cnt < 0 || cnt > c->A.n_local) return set_error(c, CAL_ERR_ARG, "diag_gather_dev: bad arguments");
+    CAL_HIP_OTHER(c, launch_gather(dst, c->A.val, c->A.dpos, cnt, c->stream));
     return 0;
 }
 
@@ -1288,6 +1378,7 @@ int cal_timer_bytes(cal_ctx* c, const char* kind, double* bytes) {
     else if (!strcmp(kind, "allreduce")) k = 4;
     else if (!strcmp(kind, "halo")) k = 5;
     else if (!strcmp(kind, "normest")) k = 6;
+    else if (!strcmp(kind, "drive")) k = 7;
     else if (strcmp(kind, "all")) return set_error(c, CAL_ERR_ARG, "unknown timer kind");
     double b = 0.0;
     for (auto& r : c->timers)
@@ -1306,6 +1397,7 @@ int cal_timer_read(cal_ctx* c, const char* kind, int64_t* count, double* total_m
     else if (!strcmp(kind, "allreduce")) k = 4;
     else if (!strcmp(kind, "halo")) k = 5;
     else if (!strcmp(kind, "normest")) k = 6;
+    else if (!strcmp(kind, "drive")) k = 7;
     else if (strcmp(kind, "all")) return set_error(c, CAL_ERR_ARG, "unknown timer kind");
     CAL_HIP(c, hipStreamSynchronize(c->stream));
     int64_t cnt = 0;
@@ -1375,6 +1467,40 @@ int cal_set_matrix_csc(cal_ctx* c, int64_t n, const int64_t* jc, const int64_t* 
             val[q] = pr[p];
         }
     return cal_set_matrix_csr(c, n, rowptr.data(), col32.data(), val.data());
+}
+
+int cal_set_diagonal(cal_ctx* c, int64_t n, const double* d) {
+    if (!c) return CAL_ERR_ARG;
+    hipSetDevice(c->device);
+    if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    if (c->prop)
+        return set_error(c, CAL_ERR_ARG, "cal_set_diagonal: a propagator is open on the context and owns the diagonal");
+    if (c->lz || c->slz)
+        return set_error(c, CAL_ERR_ARG, "cal_set_diagonal: a Lanczos run is open on the context (end it first)");
+    if (!d || n != c->A.n_local) return set_error(c, CAL_ERR_ARG, "cal_set_diagonal: need d with n_local entries");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(d[i])) return set_error(c, CAL_ERR_ARG, "cal_set_diagonal: non-finite entry in d");
+    CAL_TRY(diag_positions(c));  // refusals leave the matrix untouched
+    CAL_TRY(ensure_scratch(c, (size_t)n));
+    CAL_HIP(c, hipMemcpyAsync(c->d_scratch, d, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_TRY(diag_update_dev(c, c->d_scratch, n, 1, 0, nullptr, 0, nullptr));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));  // d is the caller's
+    return 0;
+}
+
+int cal_get_diagonal(cal_ctx* c, int64_t n, double* d) {
+    if (!c) return CAL_ERR_ARG;
+    hipSetDevice(c->device);
+    if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    if ((c->lz && !c->prop) || c->slz)
+        return set_error(c, CAL_ERR_ARG, "cal_get_diagonal: a Lanczos run is open on the context (end it first)");
+    if (!d || n != c->A.n_local) return set_error(c, CAL_ERR_ARG, "cal_get_diagonal: need d with n_local entries");
+    CAL_TRY(diag_positions(c));
+    CAL_TRY(ensure_scratch(c, (size_t)n));
+    CAL_TRY(diag_gather_dev(c, c->d_scratch, n));
+    CAL_HIP(c, hipMemcpyAsync(d, c->d_scratch, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int cal_set_spmv_format(cal_ctx* c, const char* fmt) {

@@ -52,7 +52,9 @@ const char* cal_last_error(const cal_ctx* ctx);
 int cal_synchronize(cal_ctx* ctx);
 /* Kernel-duration timer (HIP events on the context stream).  kind: "spmv",
  * "gram", "apply", "other", "allreduce", "halo" (the RCCL calls), "normest"
- * (the span of the implicit restart's normest on its own stream), "all".
+ * (the span of the implicit restart's normest on its own stream), "drive"
+ * (the kernel that rewrites the diagonal: cal_set_diagonal, one launch per
+ * driven time step), "all".
  * Returns the number of launches timed and their summed duration since the
  * last reset. */
 int cal_timer_enable(cal_ctx* ctx, int on);
@@ -84,6 +86,24 @@ int cal_set_matrix_csr_stacked(cal_ctx* ctx, int64_t n, const int64_t* rowptr, c
 int cal_set_matrix_csr_dist(cal_ctx* ctx, int64_t n_global, int64_t row0, int64_t nlocal,
                             const int64_t* rowptr, const int64_t* colind_global, const double* val);
 int cal_matrix_info(cal_ctx* ctx, int64_t* n_local, int64_t* nnz_local, int64_t* n_global, int64_t* nghost);
+/* Rewrite / read the stored diagonal of the resident matrix in place: no new
+ * upload, no new format analysis, every device pointer unchanged.  n must
+ * equal n_local; d has one entry per row (the entry with col == row).  The
+ * positions are looked up on the device at the first call on a matrix (one
+ * host wait), later calls only enqueue.  cal_set_diagonal takes effect for
+ * every later call on the context.
+ * CAL_ERR_UNSUPPORTED (nothing is written, the message names the cause): a
+ * communicator of several ranks or a slab of a distributed matrix; a matrix on
+ * the row-pattern format (its values live in pattern tables: select "csr" or
+ * "split" with cal_set_spmv_format before the matrix is set -- under "auto"
+ * that includes the plain Laplacians, which need "split"); a row that stores
+ * no diagonal entry, or more than one (an explicit 0.0 counts as stored).
+ * CAL_ERR_ARG: a non-finite d, a wrong n, or a cal_lanczos_begin /
+ * cal_std_lanczos_begin run open on the context; cal_set_diagonal also while
+ * a propagator is open (it owns the diagonal; cal_get_diagonal is allowed
+ * there and reads the 2n entries of blkdiag(H, H) as the last step left them). */
+int cal_set_diagonal(cal_ctx* ctx, int64_t n, const double* d);
+int cal_get_diagonal(cal_ctx* ctx, int64_t n, double* d);
 /* CA matrix-powers kernel of a distributed banded matrix (window halo layout,
  * row-pattern format): each slab also stores the rows of its (depth-1)-band
  * deep ghost zone, so the s <= depth powers of matrix_powers_* / one
@@ -372,6 +392,35 @@ int cal_prop_get_observables(cal_ctx* ctx, int64_t first, int64_t count, double*
 int cal_prop_combine_obs(cal_ctx* ctx, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
                          int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
                          double* out_re, double* out_im, double* norm2, double* sums);
+
+/* ---- a time-dependent potential H(t) = H0 + sum_k f_k(t) diag(W_k) ---- */
+/* W: n x nk column-major real diagonal operators, 0 <= nk <= 4, copied to the
+ * device.  H0's diagonal V0 is taken from the context's matrix as it is at
+ * this call and kept on the device; from then on the propagator owns the
+ * diagonal.  nk = 0 switches the drive off and puts V0 back; cal_prop_end and
+ * a new cal_prop_begin do the same, so the matrix is left as the caller set
+ * it.  Needs an active propagator (CAL_ERR_ARG without one, or with nk outside
+ * the cap or a non-finite W); CAL_ERR_UNSUPPORTED as cal_set_diagonal, with
+ * the matrix and an earlier drive untouched. */
+int cal_prop_set_drive(cal_ctx* ctx, int nk, const double* W);
+/* cal_prop_step under the drive: before time step it = 0 .. nsteps-1 one
+ * kernel sets, in both halves of blkdiag(H, H), row i's diagonal to
+ *   d = V0[i];  for k = 0 .. nk-1 (ascending):  p = f[it*ldf + k] * W_k[i];  d = d + p
+ * (product and sum rounded separately: a NumPy loop reproduces the bits), then
+ * the step is exactly cal_prop_step's.  ldf >= nk; a non-finite amplitude in
+ * the nsteps rows is CAL_ERR_ARG before anything runs.  The library does not
+ * interpret the rows of f: at which times they are sampled is the caller's
+ * integration scheme (the midpoint rule takes f(t + dt/2)).  The energy an
+ * observables row records is <psi'|H|psi'> with the H of that step.
+ * cal_prop_step keeps working while a drive is set: it steps under whatever H
+ * the last driven step left (H0 before the first).  The Newton shifts stay
+ * those of the first step unless cal_prop_refresh_shifts is called. */
+int cal_prop_step_driven(cal_ctx* ctx, double dt, double tol, int adaptive, int nsteps, const double* f, int ldf);
+/* Forget the Newton shifts the first step's prologue (or eigest) left: the
+ * next step's prologue computes them from the current H and state.  Right
+ * after a drive has moved H's spectrum by an amount comparable to its width;
+ * unnecessary for a drive small against it.  No-op for the monomial basis. */
+int cal_prop_refresh_shifts(cal_ctx* ctx);
 
 /* [T,Q,lsteps] = ca_lanczos_prop(A,r0,s,m,dt,tol,basis,eigest,adaptive)
  * (ca_lanczos_prop.m:3-135) with r0 = r_re + i r_im (r_im may be NULL) on the

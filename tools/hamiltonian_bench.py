@@ -5,6 +5,7 @@ the same matrix on CSR and against the plain Laplacian's plane march.
   python tools/hamiltonian_bench.py [--N 215] [--rounds 2] [--windows 5]
                                     [--only spmv,ca,lanczos,prop]
                                     [--library NAME] [--out profiles/dsplit/NAME.json]
+                                    [--drive LIST] [--package-root DIR]
 
 Matrix: grid_hamiltonian((N, N, N), V) with the harmonic potential V = 0.5 w^2
 |x - x0|^2 (w = 0.02: V of the size of the kinetic term), h = mass = 1, so the
@@ -22,6 +23,17 @@ A child measures, in --windows (>= 5) windows each after a warm-up:
            tools/lanczos_bench.py;
   prop     the propagator on blkdiag(H, H), s = 8, 3 blocks, 4 time steps per
            window, as tools/prop_bench.py.
+--drive LIST (comma separated, default 0) runs the prop leg once per entry, each
+in a child of its own ("VARIANT+driveK"): 0 undriven; NK = 1 .. 4 under the
+drive H(t) = H0 + sum_k f_k(t) diag(W_k) with NK operators (the coordinates
+about the centre, then r^2; midpoint amplitudes 1e-3 sin((k + 1) t)), where the
+child also reports the drive kernel's own time (the library's "drive" timer
+class over 10 driven steps) and its rate over the bytes the library counts,
+(8 (1 + NK) + 4 * 2) n in + 16 * 2 * n out (8 * 2 * n on CSR); "reupload"
+is what the drive replaces, set_matrix_stacked of the new H (the diagonal
+rewritten in the host's CSR copy) before every step, 2 steps per window.
+--package-root DIR adds the undriven prop leg from another checkout's built
+package ("VARIANT@root", e.g. the parent commit's, to show it unchanged).
 The summary has median, min and max over all windows of a variant and, for
 split against csr, whether split is faster beyond the spread of both (split's
 slowest window under csr's fastest).  --library runs the children on another
@@ -59,6 +71,8 @@ def build(cal, np, variant, N):
 def child(a):
     import numpy as np
 
+    if a.package_root:
+        sys.path.insert(0, os.path.abspath(a.package_root))
     import ca_lanczos_amd as cal
     from ca_lanczos_amd import _lib
 
@@ -67,7 +81,8 @@ def child(a):
     n = A.shape[0]
     fmt = {"split": "split", "csr": "csr", "lap": "auto"}[a.variant]
     ctx = cal.Context(spmv_format=fmt).set_matrix(A)
-    out = dict(variant=a.variant, library=os.path.basename(_lib.LIB_PATH), n=n, nnz=int(A.nnz),
+    out = dict(variant=a.variant, library=os.path.basename(_lib.LIB_PATH), package=os.path.relpath(os.path.dirname(cal.__file__), ROOT),
+               drive=a.drive, n=n, nnz=int(A.nnz),
                spmv_format=ctx.spmv_format(), plane_info=ctx.spmv_plane_info(), split_info=ctx.spmv_split_info())
     only = a.only.split(",")
     if "spmv" in only:
@@ -119,34 +134,84 @@ def child(a):
         P = cal.Propagator(A, psi0, S, BLOCKS, basis="newton", ctx=ctx)
         out["stacked_split_info"] = ctx.spmv_split_info()
         out["stacked_plane_info"] = ctx.spmv_plane_info()
-        P.step(a.dt, 2)
+        nk = int(a.drive) if a.drive.isdigit() else 0
+        per_window = PROP_PER_WINDOW
+        if nk > 0 or a.drive == "reupload":
+            idx = np.arange(n)
+            cc = [(idx // N ** d) % N - 0.5 * (N - 1) for d in range(3)]
+            ops = (cc + [sum(c * c for c in cc)])[:max(nk, 1)]
+            del idx, cc
+
+            def amp(t):
+                return np.array([1e-3 * np.sin((k + 1) * t) for k in range(len(ops))])
+        if nk > 0:
+            P.set_drive(ops)
+
+            def steps(k):
+                P.step(a.dt, k, drive=amp)
+        elif a.drive == "reupload":
+            per_window = 2
+            rows = np.repeat(np.arange(n), np.diff(A.indptr))
+            dpos = np.nonzero(rows == A.indices)[0]
+            del rows
+            d0 = A.data[dpos].copy()
+            Hn = A.copy()
+
+            def steps(k):
+                for _ in range(k):
+                    Hn.data[dpos] = d0 + amp(P.t + 0.5 * a.dt)[0] * ops[0]
+                    ctx.set_matrix_stacked(Hn)
+                    P.step(a.dt, 1)
+        else:
+            def steps(k):
+                P.step(a.dt, k)
+        steps(2)
         ctx.synchronize()
         ms = []
         for _ in range(W):
             t0 = time.perf_counter()
-            P.step(a.dt, PROP_PER_WINDOW)
+            steps(per_window)
             ctx.synchronize()
-            ms.append(1e3 * (time.perf_counter() - t0) / PROP_PER_WINDOW)
+            ms.append(1e3 * (time.perf_counter() - t0) / per_window)
+        if nk > 0:  # the drive kernel alone: its own timer class over 10 driven steps
+            K = 10
+            ctx.timer_enable(True)
+            ctx.timer_reset()
+            steps(K)
+            ctx.synchronize()
+            cnt, tot = ctx.timer_read("drive")
+            bytes_counted = ctx.timer_bytes("drive")
+            ctx.timer_enable(False)
+            us = 1e3 * tot / cnt
+            out["drive_kernel"] = dict(us=us, launches_per_step=cnt / K, bytes=bytes_counted / cnt,
+                                       TBps=bytes_counted / cnt / (us * 1e-6) / 1e12)
         info = P.info()
         out["prop_ms_per_step"] = ms
         out["prop_lsteps"] = info["lsteps"]
         out["prop_residual_max"] = info["residual_max"]
+        # what a step's cost depends on besides the kernels' rates: the Lanczos vectors taken
+        # (dropped blocks shorten a step) and the blocks' orthogonalisation path
+        out["prop_info"] = {k: info[k] for k in ("steps", "lsteps_sum", "lsteps_max", "breakdowns", "rank_deficient")}
+        out["prop_tsqr_fold_stats"] = ctx.tsqr_fold_stats()
         P.close()
         ctx.close()
     print(json.dumps(out))
 
 
-def run_child(a, variant):
+def run_child(a, variant, drive="0", root=None):
     env = dict(os.environ)
     env.pop("CAL_LIBRARY", None)
     env.pop("CAL_SPMV_FORMAT", None)
     if a.library:
         env["CAL_LIBRARY"] = a.library
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--variant", variant, "--N", str(a.N),
-           "--windows", str(a.windows), "--only", a.only, "--dt", str(a.dt)]
+           "--windows", str(a.windows), "--only", a.only if drive == "0" and not root else "prop", "--dt", str(a.dt),
+           "--drive", drive]
+    if root:
+        cmd += ["--package-root", root]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
     if p.returncode != 0:
-        raise RuntimeError("child %s failed (%d): %s" % (variant, p.returncode, p.stderr[-2000:]))
+        raise RuntimeError("child %s drive %s failed (%d): %s" % (variant, drive, p.returncode, p.stderr[-2000:]))
     return json.loads(p.stdout.strip().splitlines()[-1])
 
 
@@ -159,6 +224,8 @@ def main():
     ap.add_argument("--variants", default="split,csr,lap")
     ap.add_argument("--dt", type=float, default=0.05)
     ap.add_argument("--library", default=None)
+    ap.add_argument("--drive", default="0", help="prop leg: comma list of 0, 1..4 (operators) or reupload")
+    ap.add_argument("--package-root", default=None, help="also the undriven prop leg from this checkout's package")
     ap.add_argument("--child-timeout", type=int, default=500)
     ap.add_argument("--variant", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -170,12 +237,21 @@ def main():
         return child(a)
 
     variants = a.variants.split(",")
+    drives = a.drive.split(",")
+    for d in drives:
+        if d not in ("0", "1", "2", "3", "4", "reupload"):
+            ap.error("--drive takes 0, 1..4 or reupload")
+    legs = [(v, v, "0", None) for v in variants] if "0" in drives else []
+    legs += [("%s+drive%s" % (v, d), v, d, None) for v in variants if v != "lap" for d in drives if d != "0"]
+    if a.package_root:
+        legs += [("%s@root" % v, v, "0", a.package_root) for v in variants]
+    variants = [l[0] for l in legs]
     res = dict(N=a.N, n=a.N ** 3, rounds=a.rounds, windows=a.windows, only=a.only, library=a.library or "production",
                s=S, blocks=BLOCKS, runs={v: [] for v in variants})
     for i in range(a.rounds):  # alternating, each in a fresh process
-        for v in variants:
-            res["runs"][v].append(run_child(a, v))
-            print("round %d: %s done" % (i + 1, v), file=sys.stderr, flush=True)
+        for name, v, d, root in legs:
+            res["runs"][name].append(run_child(a, v, d, root))
+            print("round %d: %s done" % (i + 1, name), file=sys.stderr, flush=True)
 
     keys = dict(spmv="spmv_us", ca="ca_ms_per_outer", lanczos="lanczos_ms_per_vector", prop="prop_ms_per_step")
     summ = {}
@@ -186,6 +262,12 @@ def main():
             if w:
                 med = statistics.median(w)
                 summ[v][k] = dict(median=med, min=min(w), max=max(w), windows=len(w), per_s=1e3 / med if k != "spmv" else None)
+    for v in variants:
+        dk = [r["drive_kernel"] for r in res["runs"][v] if "drive_kernel" in r]
+        if dk:
+            summ[v]["drive_kernel"] = dict(us=statistics.median(x["us"] for x in dk), us_all=[x["us"] for x in dk],
+                                           bytes=dk[0]["bytes"],
+                                           TBps=dk[0]["bytes"] / (statistics.median(x["us"] for x in dk) * 1e-6) / 1e12)
     res["summary"] = summ
     n = a.N ** 3
     for v in variants:
