@@ -151,6 +151,10 @@ SIGNATURES = [
     ("cal_prop_get_observables", c_int, [c_void_p, c_int64, c_int64, dp, POINTER(c_int64), ip]),
     ("cal_prop_combine_obs", c_int,
      [c_void_p, c_int64, c_int, dp, dp, dp, c_int, dp, c_int, dp, dp, dp, dp, dp, dp]),
+    ("cal_prop_set_absorber", c_int, [c_void_p, dp]),
+    ("cal_prop_get_absorbed", c_int, [c_void_p, c_int64, c_int64, dp, POINTER(c_int64)]),
+    ("cal_prop_combine_masked", c_int,
+     [c_void_p, c_int64, c_int, dp, dp, dp, dp, c_int, dp, c_int, dp, dp, dp, dp, dp, dp, dp]),
     ("cal_set_diagonal", c_int, [c_void_p, c_int64, dp]),
     ("cal_get_diagonal", c_int, [c_void_p, c_int64, dp]),
     ("cal_prop_set_drive", c_int, [c_void_p, c_int, dp]),

@@ -225,6 +225,32 @@ class Context:
         ov = sums[nw:nw + 2 * nphi]
         return ore + 1j * oim, n2.value, sums[:nw].copy(), ov[0::2] + 1j * ov[1::2]
 
+    def prop_combine_masked(self, Q, c, mask, W=None, phi=None):
+        """``prop_combine_obs`` through the kernel that multiplies the result
+        by a real mask in [0, 1] before it is stored (cal_prop_combine_masked):
+        with u = ``prop_combine(Q, c)``, out = mask * u.  Returns (out, norm2,
+        absorbed = sum (1 - mask^2) |u|^2, <W_k>, <phi_r|out>); norm2 and the
+        observables are those of out."""
+        Q = f64(Q)
+        n, m = Q.shape[0] // 2, Q.shape[1]
+        c = np.asarray(c, dtype=np.complex128).ravel()
+        cre, cim = np.ascontiguousarray(c.real), np.ascontiguousarray(c.imag)
+        mk = np.ascontiguousarray(mask, dtype=np.float64).ravel()
+        if mk.shape[0] != n:
+            raise ValueError("the mask needs n entries")
+        Wm, pre, pim = _obs_arrays(n, W, phi)
+        nw, nphi = Wm.shape[1], pre.shape[1]
+        ore, oim = np.zeros(n), np.zeros(n)
+        sums = np.zeros(max(nw + 2 * nphi, 1))
+        n2, ab = ctypes.c_double(), ctypes.c_double()
+        check(self.h, lib.cal_prop_combine_masked(self.h, n, m, ptr(Q), ptr(cre), ptr(cim), ptr(mk), nw,
+                                                  ptr(Wm) if nw else None, nphi, ptr(pre) if nphi else None,
+                                                  ptr(pim) if nphi else None, ptr(ore), ptr(oim),
+                                                  ctypes.cast(ctypes.byref(n2), dp), ctypes.cast(ctypes.byref(ab), dp),
+                                                  ptr(sums)), "prop_combine_masked")
+        ov = sums[nw:nw + 2 * nphi]
+        return ore + 1j * oim, n2.value, ab.value, sums[:nw].copy(), ov[0::2] + 1j * ov[1::2]
+
     def set_diagonal(self, d):
         """Rewrite the stored diagonal of the resident matrix in place
         (cal_set_diagonal): one entry per row, no new upload or analysis.
@@ -1055,6 +1081,39 @@ class Propagator:
         ov = rows[:, 3 + nw:]
         return dict(t=rows[:, 0].copy(), norm2=rows[:, 1].copy(), energy=rows[:, 2].copy(),
                     W=rows[:, 3:3 + nw].copy(), overlap=ov[:, 0::2] + 1j * ov[:, 1::2])
+
+    def set_absorber(self, mask):
+        """An absorbing boundary: from now on every completed time step (each
+        sub-step of ``scheme="cf4"`` too) ends with ``psi <- mask * psi``
+        inside the combine sweep, mask real with n values in [0, 1]
+        (``matrices.absorber_mask``), and the squared norm it removes,
+        ``sum (1 - mask^2) |psi|^2``, is recorded (``absorbed``).  This is the
+        first-order splitting of a complex absorbing potential
+        ``-ln(mask)/dt``: a mask belongs to the dt it is stepped with.  The
+        observables, the energy and ``info()["norm"]`` are those of the masked
+        state.  Replaces an earlier mask and clears the absorbed history;
+        ``None`` switches the absorber off."""
+        if not getattr(self, "_open", False):
+            raise CalError(_lib.CAL_ERR_ARG, "set_absorber: the propagator is closed")
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(mask, dtype=np.float64).ravel()
+            if mk.shape[0] != self.n:
+                raise ValueError("the mask must have H.shape[0] entries")
+        check(self.ctx.h, lib.cal_prop_set_absorber(self.ctx.h, ptr(mk)), "prop_set_absorber")
+        return self
+
+    def absorbed(self, first=0, count=None):
+        """The squared norm the mask removed, one entry per completed step
+        since ``set_absorber`` (rows [first, first + count); default all):
+        dict of ``t`` and ``absorbed``."""
+        nr = ctypes.c_int64()
+        check(self.ctx.h, lib.cal_prop_get_absorbed(self.ctx.h, 0, 0, None, ctypes.byref(nr)), "prop_get_absorbed")
+        count = nr.value - first if count is None else count
+        rows = np.zeros((max(count, 0), 2))
+        check(self.ctx.h, lib.cal_prop_get_absorbed(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr)),
+              "prop_get_absorbed")
+        return dict(t=rows[:, 0].copy(), absorbed=rows[:, 1].copy())
 
     def close(self):
         if getattr(self, "_open", False):

@@ -544,6 +544,15 @@ struct PropObs {
 };
 hipError_t launch_prop_combine_obs(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
                                    double* out, double* partial, const PropObs& o, hipStream_t st);
+// The same sweep under an absorbing mask (k_prop_combine's ABS flag): with u
+// the row's two sums, out = mask .* u is stored, the squared norm and the
+// observables are those of out, and one more quantity, index 1 + nw + 2 np
+// (launch_reduce over 2 + nw + 2 np), is sum (1 - mask^2) |u|^2.  mask: n
+// doubles, 16-byte aligned, in an allocation of an even ldm >= n doubles (the
+// pad is not read).  o.nw = o.np = 0 takes the kernels without observables.
+hipError_t launch_prop_combine_masked(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
+                                      double* out, double* partial, const PropObs& o, const double* mask,
+                                      int64_t ldm, hipStream_t st);
 
 // ---- the time-dependent diagonal H(t) = H0 + sum_k f_k(t) diag(W_k) (prop.hip) ----
 // k_diag_find: dpos[r] = the position in val of row r's first entry with

@@ -18,6 +18,9 @@
 // (cal_prop_set_drive / cal_prop_step_driven) rewrites the matrix's stored
 // diagonal in place before each step (prop.hip k_diag_drive through
 // runtime.cpp diag_update_dev): the step itself is unchanged.
+// An absorbing mask (cal_prop_set_absorber) multiplies the state by a real
+// diagonal 0 <= M <= 1 at the end of every step, inside the combine sweep
+// (prop.hip's ABS flag), and records the squared norm it removes.
 // The one deliberate difference from ca_lanczos_prop.m: :78 projects with
 // doreorth = false, the blocks here apply the library's second-pass rule
 // (projectAndNormalize's 'second'), which is at least as orthogonal.
@@ -67,7 +70,13 @@ struct PropState {
     double* d_drv = nullptr;     // W (nk columns of ldd doubles)
     int64_t ldd = 0;             // roundup(n, 64)
     uint64_t drv_gen = 0;
+    // the absorbing mask (cal_prop_set_absorber): a library-owned copy, applied
+    // by the combine sweep; one row [t, absorbed] per completed step since the set
+    double* d_mask = nullptr;    // ldm doubles
+    int64_t ldm = 0;             // roundup(n, 64)
+    std::vector<double> ahist;
     bool obs_on() const { return nw > 0 || nphi > 0 || energy; }
+    bool abs_on() const { return d_mask != nullptr; }
     int nq() const { return nw + 2 * nphi; }
     double* psi(const cal_ctx* c) const { return d_psi + c->A.lpad; }
 };
@@ -104,10 +113,18 @@ int drive_off(cal_ctx* c, PropState& P) {
     return st;
 }
 
+void abs_free(PropState& P) {
+    if (P.d_mask) hipFree(P.d_mask);
+    P.d_mask = nullptr;
+    P.ldm = 0;
+    P.ahist.clear();
+}
+
 void prop_free(cal_ctx* c) {
     if (!c || !c->prop) return;
     drive_off(c, *c->prop);
     obs_free(*c->prop);
+    abs_free(*c->prop);
     if (c->prop->d_psi) hipFree(c->prop->d_psi);
     if (c->prop->d_coef) hipFree(c->prop->d_coef);
     if (c->prop->h_coef) hipHostFree(c->prop->h_coef);
@@ -122,7 +139,8 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     CAL_HIP_OTHER(c, hipMemcpyAsync(P.d_coef, P.h_coef, 2 * kPropMaxCols * sizeof(double), hipMemcpyHostToDevice,
                                     c->stream));
     const int nb = prop_combine_blocks(P.n);
-    if (!P.obs_on()) {
+    const int na = P.abs_on() ? 1 : 0;
+    if (!P.obs_on() && !na) {
         CAL_TRY(ensure_partial(c, nb));
         CAL_TRY(ensure_red(c, 1));
         const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n) * 8.0);
@@ -137,13 +155,14 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
         P.nrm2 = P.h_coef[2 * kPropMaxCols];
         return 0;
     }
-    // with observables: d_red = [psi'psi, the nw + 2 nphi sums, the energy],
-    // fetched with the squared norm in the one pinned transfer
+    // with observables or an absorber: d_red = [psi'psi, the nw + 2 nphi sums,
+    // the absorbed norm (absorber on), the energy], fetched with the squared
+    // norm in the one pinned transfer
     const int nq = P.nq();
     const int nd = dot_blocks(2 * P.n);
-    const size_t pe = (size_t)(1 + nq) * nb;  // the energy's partials follow the combine's
+    const size_t pe = (size_t)(1 + nq + na) * nb;  // the energy's partials follow the combine's
     CAL_TRY(ensure_partial(c, pe + (size_t)std::max(P.eparts, nd)));
-    CAL_TRY(ensure_red(c, (size_t)nq + 2));
+    CAL_TRY(ensure_red(c, (size_t)nq + na + 2));
     PropObs o;
     o.W = P.d_obs;
     o.pr = P.d_obs + (size_t)P.nw * P.ldo;
@@ -151,12 +170,16 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     o.ld = P.ldo;
     o.nw = P.nw;
     o.np = P.nphi;
-    const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n + (double)P.n * (P.nw + 2 * P.nphi)) * 8.0);
-    const hipError_t e = launch_prop_combine_obs(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c),
-                                                 c->d_partial, o, c->stream);
+    const int t = timer_begin(
+        c, 2, ((double)2 * P.n * m + (double)2 * P.n + (double)P.n * (P.nw + 2 * P.nphi) + (double)P.n * na) * 8.0);
+    const hipError_t e =
+        na ? launch_prop_combine_masked(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c), c->d_partial, o,
+                                        P.d_mask, P.ldm, c->stream)
+           : launch_prop_combine_obs(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c), c->d_partial, o,
+                                     c->stream);
     timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine_obs");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1 + nq, c->d_red, c->stream));
+    if (e != hipSuccess) return hip_fail(c, e, na ? "launch_prop_combine_masked" : "launch_prop_combine_obs");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1 + nq + na, c->d_red, c->stream));
     if (P.energy) {
         // <psi'|H|psi'> = y'x over the stacked rows, y = blkdiag(H, H) x: the
         // fused Lanczos mode's dot, reduced as lanczos_std.cpp reduces it
@@ -164,15 +187,15 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
         double* part = c->d_partial + pe;
         if (P.eparts > 0) {
             CAL_TRY(spmv_lanczos_dev(c, P.psi(c), nullptr, nullptr, y, part));
-            CAL_HIP_OTHER(c, launch_reduce(part, P.eparts, 1, c->d_red + 1 + nq, c->stream));
+            CAL_HIP_OTHER(c, launch_reduce(part, P.eparts, 1, c->d_red + 1 + nq + na, c->stream));
         } else {
             CAL_TRY(spmv_dev(c, P.psi(c), y, 0, 0.0, 0.0, nullptr));
             CAL_HIP_OTHER(c, launch_dot(y, P.psi(c), 2 * P.n, part, nd, c->stream));
-            CAL_HIP_OTHER(c, launch_reduce(part, nd, 1, c->d_red + 1 + nq, c->stream));
+            CAL_HIP_OTHER(c, launch_reduce(part, nd, 1, c->d_red + 1 + nq + na, c->stream));
         }
     }
     double* h = P.h_coef + 2 * kPropMaxCols;
-    CAL_HIP_OTHER(c, hipMemcpyAsync(h, c->d_red, (size_t)(nq + (P.energy ? 2 : 1)) * sizeof(double),
+    CAL_HIP_OTHER(c, hipMemcpyAsync(h, c->d_red, (size_t)(nq + na + (P.energy ? 2 : 1)) * sizeof(double),
                                     hipMemcpyDeviceToHost, c->stream));
     CAL_HIP(c, hipStreamSynchronize(c->stream));
     P.nrm2 = h[0];
@@ -185,8 +208,14 @@ void record_row(PropState& P) {
     const int nq = P.nq();
     P.hist.push_back(P.t);
     P.hist.push_back(h[0]);
-    P.hist.push_back(P.energy ? h[1 + nq] : std::numeric_limits<double>::quiet_NaN());
+    P.hist.push_back(P.energy ? h[1 + nq + (P.abs_on() ? 1 : 0)] : std::numeric_limits<double>::quiet_NaN());
     P.hist.insert(P.hist.end(), h + 1, h + 1 + nq);
+}
+
+// the absorber's row [t, absorbed] of the step just completed
+void record_absorbed(PropState& P) {
+    P.ahist.push_back(P.t);
+    P.ahist.push_back(P.h_coef[2 * kPropMaxCols + 1 + P.nq()]);
 }
 
 // One Krylov build from the current state: CA blocks until max_blocks, the
@@ -445,6 +474,108 @@ int cal_prop_get_observables(cal_ctx* c, int64_t first, int64_t count, double* o
     return 0;
 }
 
+// every value finite and in [0, 1] (NaN fails both comparisons)
+static bool mask_ok(const double* mask, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(mask[i] >= 0.0 && mask[i] <= 1.0)) return false;
+    return true;
+}
+
+int cal_prop_combine_masked(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
+                            const double* mask, int nw, const double* W, int nphi, const double* phi_re,
+                            const double* phi_im, double* out_re, double* out_im, double* norm2, double* absorbed,
+                            double* sums) {
+    if (!c) return CAL_ERR_ARG;
+    hipSetDevice(c->device);
+    if (n < 1 || m < 1 || m > kPropMaxCols || !Q || !c_re || !c_im || !mask || !out_re || !out_im)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_combine_masked: need n >= 1, 1 <= m <= 512 and non-null arrays");
+    const int nq = nw + 2 * nphi;
+    if (!obs_counts_ok(nw, W, nphi, phi_re) || (nq > 0 && !sums))
+        return set_error(c, CAL_ERR_ARG,
+                         "cal_prop_combine_masked: need 0 <= nw, nphi <= 4 with their arrays and sums");
+    if (!mask_ok(mask, n))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_combine_masked: the mask must be finite and within [0, 1]");
+    const int64_t ld = ((2 * n + 63) / 64) * 64;
+    const int64_t ldo = ((n + 63) / 64) * 64;
+    const int nb = prop_combine_blocks(n);
+    // Q (ld x m), out (ld), W and phi (ldo x nq), the mask (ldo), the coefficients (2 m)
+    CAL_TRY(ensure_scratch(c, (size_t)ld * (m + 1) + (size_t)ldo * (nq + 1) + 2 * (size_t)m));
+    CAL_TRY(ensure_partial(c, (size_t)(2 + nq) * nb));
+    CAL_TRY(ensure_red(c, (size_t)nq + 2));
+    double* dQ = c->d_scratch;
+    double* dout = dQ + (size_t)ld * m;
+    double* dobs = dout + ld;
+    double* dmask = dobs + (size_t)ldo * nq;
+    double* dco = dmask + ldo;
+    CAL_HIP(c, hipMemcpy2DAsync(dQ, ld * sizeof(double), Q, 2 * n * sizeof(double), 2 * n * sizeof(double), m,
+                                hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco, c_re, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dmask, mask, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_TRY(upload_obs(c, dobs, ldo, n, nw, W, nphi, phi_re, phi_im));
+    PropObs o;
+    o.W = dobs;
+    o.pr = dobs + (size_t)nw * ldo;
+    o.pi = dobs + (size_t)(nw + nphi) * ldo;
+    o.ld = ldo;
+    o.nw = nw;
+    o.np = nphi;
+    const int t = timer_begin(c, 2, ((double)2 * n * m + (double)2 * n + (double)n * nq + (double)n) * 8.0);
+    const hipError_t e =
+        launch_prop_combine_masked(dQ, ld, n, m, dco, dco + m, dout, c->d_partial, o, dmask, ldo, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine_masked");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 2 + nq, c->d_red, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out_re, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out_im, dout + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    double red[2 + 3 * kPropMaxObs] = {0.0};
+    CAL_HIP(c, hipMemcpyAsync(red, c->d_red, (size_t)(2 + nq) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    if (norm2) *norm2 = red[0];
+    for (int q = 0; q < nq; ++q) sums[q] = red[1 + q];
+    if (absorbed) *absorbed = red[1 + nq];
+    return 0;
+}
+
+int cal_prop_set_absorber(cal_ctx* c, const double* mask) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_set_absorber: no active propagator");
+    hipSetDevice(c->device);
+    PropState& P = *c->prop;
+    if (mask && !mask_ok(mask, P.n))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_set_absorber: the mask must be finite and within [0, 1]");
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    if (!mask) {
+        abs_free(P);
+        return 0;
+    }
+    // the new copy first: a failure leaves an earlier absorber as it was
+    const int64_t ldm = ((P.n + 63) / 64) * 64;
+    double* d = nullptr;
+    CAL_HIP(c, hipMalloc((void**)&d, ldm * sizeof(double)));
+    if (hipMemsetAsync(d, 0, ldm * sizeof(double), c->stream) != hipSuccess ||
+        hipMemcpyAsync(d, mask, P.n * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {  // the source is the caller's
+        hipFree(d);
+        return set_error(c, CAL_ERR_HIP, "cal_prop_set_absorber: upload failed");
+    }
+    abs_free(P);
+    P.d_mask = d;
+    P.ldm = ldm;
+    return 0;
+}
+
+int cal_prop_get_absorbed(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_get_absorbed: no active propagator");
+    const PropState& P = *c->prop;
+    const int64_t nr = (int64_t)(P.ahist.size() / 2);
+    if (nrows) *nrows = nr;
+    if (!out) return 0;
+    if (first < 0 || count < 0 || first + count > nr)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_get_absorbed: rows [first, first + count) out of range");
+    std::memcpy(out, P.ahist.data() + (size_t)first * 2, (size_t)count * 2 * sizeof(double));
+    return 0;
+}
+
 static int prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* psi_im, int s, int max_blocks,
                       const char* basis, const double* eigest, int neig) {
     bool newton = false;
@@ -555,6 +686,7 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
         if (status < 0) break;
         P.t += dt;
         if (P.obs_on()) record_row(P);
+        if (P.abs_on()) record_absorbed(P);
         P.info.steps++;
         P.info.lsteps = ks;
         P.info.lsteps_max = std::max(P.info.lsteps_max, ks);

@@ -37,6 +37,21 @@
 // The counts are kernel arguments; the loops over them are unrolled to the
 // cap with wave-uniform guards, so every accumulator is a register.  The nrm
 // chain and the stores are those of OBS = false: same state, same norm bits.
+//
+// ABS = true (launch_prop_combine_masked) multiplies the new state by a real
+// diagonal mask 0 <= M <= 1 before it is stored (the absorbing boundary: the
+// first-order splitting of a complex absorbing potential -ln(M)/dt) and sums
+// what the mask removes.  The mask is streamed once from the library's own
+// aligned copy (even leading dimension >= n; a row pair with one 16-byte load,
+// the odd last row with an 8-byte load; the pad is never read).  Per row, with
+// ut, ub the two accumulators after the j loop and m the row's mask value:
+//   d = ut*ut;  d = d + ub*ub;  p = m*m;  g = 1.0 - p;  accA = accA + g*d
+//   t = m*ut;   b = m*ub;       store t, b
+// and the nrm chain and the observables then run on t, b as written above: they
+// are those of the state as stored.  accA takes a lane's rows in row order, pair
+// by pair, then the nrm chain's wave tree and wave order; its block partial is
+// quantity 1 + nw + 2 np (after the observables; 1 without OBS).  ABS = false
+// is the kernel as it was: the mask is an `if constexpr` away.
 #include "cal_internal.hpp"
 
 namespace cal {
@@ -80,12 +95,21 @@ __device__ __forceinline__ void store2(double* __restrict__ p, double x0, double
     }
 }
 
-// the OBS kernel's extra argument; OBS = false carries an empty one
-template <bool OBS>
+// the OBS / ABS kernels' extra argument; the plain kernel carries an empty one
+template <bool OBS, bool ABS>
 struct PropObsArg {};
 template <>
-struct PropObsArg<true> {
+struct PropObsArg<true, false> {
     PropObs o;
+};
+template <>
+struct PropObsArg<false, true> {
+    const double* mask;
+};
+template <>
+struct PropObsArg<true, true> {
+    PropObs o;
+    const double* mask;
 };
 
 struct PropObsAcc {
@@ -96,6 +120,23 @@ struct PropObsAcc {
 __device__ __forceinline__ double (*obs_wave_sums())[kPropThreads / 64] {
     __shared__ double wo[3 * kPropMaxObs][kPropThreads / 64];
     return wo;
+}
+
+// the absorbed norm's wave sums (LDS of the ABS kernels only)
+__device__ __forceinline__ double* abs_wave_sums() {
+    __shared__ double wa[kPropThreads / 64];
+    return wa;
+}
+
+// one row under the mask value m: what the mask removes goes to s, the row is scaled
+__device__ __forceinline__ void mask_row(double m, double& t, double& b, double& s) {
+    double d = t * t;
+    d = d + b * b;
+    const double p = m * m;
+    const double g = 1.0 - p;
+    s = s + g * d;
+    t = m * t;
+    b = m * b;
 }
 
 // the observables' terms of the adjacent rows r, r + 1 (PAIR) or of row r alone
@@ -144,12 +185,12 @@ __device__ __forceinline__ void obs_rows(const PropObs& o, int64_t r, double t0,
         }
 }
 
-template <bool VT, bool VB, bool OBS>
+template <bool VT, bool VB, bool OBS, bool ABS>
 __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __restrict__ Q, int64_t ld, int64_t n,
                                                                int m, const double* __restrict__ a,
                                                                const double* __restrict__ b,
                                                                double* __restrict__ out,
-                                                               double* __restrict__ partial, PropObsArg<OBS> obs) {
+                                                               double* __restrict__ partial, PropObsArg<OBS, ABS> obs) {
     __shared__ double sa[kPropMaxCols];
     __shared__ double sb[kPropMaxCols];
     __shared__ double ws[kPropThreads / 64];
@@ -166,6 +207,7 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
 
     const int64_t base = (int64_t)blockIdx.x * kPropBlockRows;
     double nrm = 0.0;
+    double absd = 0.0;
 #pragma unroll
     for (int p = 0; p < kPropPairs; ++p) {
         const int64_t r = base + 2 * ((int64_t)p * kPropThreads + threadIdx.x);
@@ -190,6 +232,12 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
                 b0 = b0 + xb0 * aj;
                 b1 = b1 + xb1 * aj;
             }
+            if constexpr (ABS) {
+                double m0, m1;
+                load2<true>(obs.mask + r, m0, m1);
+                mask_row(m0, t0, b0, absd);
+                mask_row(m1, t1, b1, absd);
+            }
             store2<VT>(out + r, t0, t1);
             store2<VB>(out + n + r, b0, b1);
             nrm = nrm + t0 * t0;
@@ -211,6 +259,7 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
                 b0 = b0 + xt0 * bj;
                 b0 = b0 + xb0 * aj;
             }
+            if constexpr (ABS) mask_row(obs.mask[r], t0, b0, absd);
             out[r] = t0;
             out[n + r] = b0;
             nrm = nrm + t0 * t0;
@@ -241,6 +290,10 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
                 }
             }
     }
+    if constexpr (ABS) {
+        absd = prop_wave_sum(absd);
+        if (lane == 0) abs_wave_sums()[wave] = absd;
+    }
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
     if constexpr (OBS) {  // thread q writes quantity q of this block
@@ -248,6 +301,12 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
         const int q = (int)threadIdx.x - 1;
         if (q >= 0 && q < obs.o.nw + 2 * obs.o.np)
             partial[(int64_t)(q + 1) * gridDim.x + blockIdx.x] = ((wo[q][0] + wo[q][1]) + wo[q][2]) + wo[q][3];
+    }
+    if constexpr (ABS) {  // after the observables: quantity 1 + nw + 2 np
+        const double* wa = abs_wave_sums();
+        int q = 1;
+        if constexpr (OBS) q = 1 + obs.o.nw + 2 * obs.o.np;
+        if (threadIdx.x == 0) partial[(int64_t)q * gridDim.x + blockIdx.x] = ((wa[0] + wa[1]) + wa[2]) + wa[3];
     }
 }
 
@@ -260,9 +319,9 @@ int prop_combine_blocks(int64_t n) {
     return (int)(b < 1 ? 1 : b);
 }
 
-template <bool OBS>
+template <bool OBS, bool ABS>
 static hipError_t launch_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                                 double* out, double* partial, PropObsArg<OBS> obs, hipStream_t st) {
+                                 double* out, double* partial, PropObsArg<OBS, ABS> obs, hipStream_t st) {
     if (n < 1 || m < 1 || m > kPropMaxCols || ld < 2 * n) return hipErrorInvalidValue;
     if (n > ((int64_t)1 << 40)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)prop_combine_blocks(n)), block(kPropThreads);
@@ -272,33 +331,55 @@ static hipError_t launch_combine(const double* Q, int64_t ld, int64_t n, int m, 
     const bool vt = even && aligned16(Q) && aligned16(out);
     const bool vb = even && aligned16(Q + n) && aligned16(out + n);
     if (vt && vb)
-        hipLaunchKernelGGL((k_prop_combine<true, true, OBS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
+        hipLaunchKernelGGL((k_prop_combine<true, true, OBS, ABS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
     else if (vt)
-        hipLaunchKernelGGL((k_prop_combine<true, false, OBS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
+        hipLaunchKernelGGL((k_prop_combine<true, false, OBS, ABS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
     else if (vb)
-        hipLaunchKernelGGL((k_prop_combine<false, true, OBS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
+        hipLaunchKernelGGL((k_prop_combine<false, true, OBS, ABS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
     else
-        hipLaunchKernelGGL((k_prop_combine<false, false, OBS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial,
+        hipLaunchKernelGGL((k_prop_combine<false, false, OBS, ABS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial,
                            obs);
     return hipGetLastError();
 }
 
 hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
                                double* out, double* partial, hipStream_t st) {
-    return launch_combine<false>(Q, ld, n, m, a, b, out, partial, PropObsArg<false>{}, st);
+    return launch_combine<false, false>(Q, ld, n, m, a, b, out, partial, PropObsArg<false, false>{}, st);
+}
+
+// the observables' counts, arrays and 16-byte loads
+static bool obs_arg_ok(const PropObs& o, int64_t n) {
+    if (o.nw < 0 || o.nw > kPropMaxObs || o.np < 0 || o.np > kPropMaxObs) return false;
+    if ((o.nw > 0 && !o.W) || (o.np > 0 && (!o.pr || !o.pi))) return false;
+    // aligned origins, an even leading dimension of at least n rows
+    if (o.nw + o.np > 0 && (o.ld < n || (o.ld & 1) != 0)) return false;
+    if ((o.nw > 0 && !aligned16(o.W)) || (o.np > 0 && (!aligned16(o.pr) || !aligned16(o.pi)))) return false;
+    return true;
 }
 
 hipError_t launch_prop_combine_obs(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
                                    double* out, double* partial, const PropObs& o, hipStream_t st) {
-    if (o.nw < 0 || o.nw > kPropMaxObs || o.np < 0 || o.np > kPropMaxObs) return hipErrorInvalidValue;
-    if ((o.nw > 0 && !o.W) || (o.np > 0 && (!o.pr || !o.pi))) return hipErrorInvalidValue;
-    // the observables' 16-byte loads: aligned origins, an even leading dimension of at least n rows
-    if (o.nw + o.np > 0 && (o.ld < n || (o.ld & 1) != 0)) return hipErrorInvalidValue;
-    if ((o.nw > 0 && !aligned16(o.W)) || (o.np > 0 && (!aligned16(o.pr) || !aligned16(o.pi))))
-        return hipErrorInvalidValue;
-    PropObsArg<true> arg;
+    if (!obs_arg_ok(o, n)) return hipErrorInvalidValue;
+    PropObsArg<true, false> arg;
     arg.o = o;
-    return launch_combine<true>(Q, ld, n, m, a, b, out, partial, arg, st);
+    return launch_combine<true, false>(Q, ld, n, m, a, b, out, partial, arg, st);
+}
+
+hipError_t launch_prop_combine_masked(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
+                                      double* out, double* partial, const PropObs& o, const double* mask,
+                                      int64_t ldm, hipStream_t st) {
+    if (!obs_arg_ok(o, n)) return hipErrorInvalidValue;
+    // the mask's 16-byte loads: the rules of the observables' columns
+    if (!mask || !aligned16(mask) || ldm < n || (ldm & 1) != 0) return hipErrorInvalidValue;
+    if (o.nw + o.np == 0) {
+        PropObsArg<false, true> arg;
+        arg.mask = mask;
+        return launch_combine<false, true>(Q, ld, n, m, a, b, out, partial, arg, st);
+    }
+    PropObsArg<true, true> arg;
+    arg.o = o;
+    arg.mask = mask;
+    return launch_combine<true, true>(Q, ld, n, m, a, b, out, partial, arg, st);
 }
 
 // ---- the time-dependent diagonal ---------------------------------------------------

@@ -94,6 +94,30 @@ def grid_hamiltonian(dims, V, h: float = 1.0, mass: float = 1.0) -> sp.csr_matri
     return sp.csr_matrix((val, col, rowptr), shape=(n, n))
 
 
+def absorber_mask(dims, width: int, power: float = 0.125) -> np.ndarray:
+    """The absorbing mask of ``Propagator.set_absorber`` on the grid ``dims``:
+    the product over the axes of ``cos(pi/2 * r)**power`` (Krause, Schafer,
+    Kulander), r the depth into the outer ``width`` points of either end scaled
+    to [0, 1] -- ``(width - e)/width`` for a point e < width points from the
+    nearer end, 0 further in -- so the mask is exactly 1.0 in the interior and
+    falls to (nearly) 0 on the outermost points.  One value per grid point,
+    in the row order of ``grid_hamiltonian(dims, ...)`` (first dimension
+    fastest)."""
+    dims = tuple(int(d) for d in dims)
+    width = int(width)
+    if not dims or min(dims) < 1 or width < 0 or not power > 0:
+        raise ValueError("absorber_mask: need positive dims, width >= 0 and power > 0")
+    mask = np.ones(1)
+    for d in dims:  # the first dimension is the fastest: it is the innermost factor
+        i = np.arange(d)
+        e = np.minimum(i, d - 1 - i)
+        r = np.clip((width - e) / float(max(width, 1)), 0.0, 1.0)
+        axis = np.clip(np.cos(0.5 * np.pi * r), 0.0, 1.0) ** float(power)
+        axis[r == 0.0] = 1.0
+        mask = np.multiply.outer(axis, mask).ravel()
+    return mask
+
+
 def laplacian_rows(dim: int, N: int, r0: int, r1: int):
     """Rows [r0, r1) of the 2-D/3-D Laplacian with global int64 columns (a
     row slab of the distributed config 4): (rowptr, col, val)."""

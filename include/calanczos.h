@@ -393,6 +393,39 @@ int cal_prop_combine_obs(cal_ctx* ctx, int64_t n, int m, const double* Q, const 
                          int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
                          double* out_re, double* out_im, double* norm2, double* sums);
 
+/* ---- an absorbing boundary: a mask applied at the end of every time step ---- */
+/* mask: n doubles, 0 <= mask[i] <= 1 (1 in the interior, ramping down towards
+ * the edge), copied to the device; NULL switches the absorber off.  From then
+ * on every completed time step (each sub-step of a driven scheme is one) ends
+ * with, inside the combine sweep,
+ *   u = nrm*Q_c*c;  psi' = mask .* u;  absorbed = sum_i (1 - mask[i]^2) |u_i|^2
+ * the observables, the energy and the squared norm that normalises the next
+ * step are those of psi', the state as stored.  This is the first-order
+ * splitting of a complex absorbing potential Gamma = -ln(mask)/dt: the mask
+ * belongs to the dt it is stepped with.  Needs an active propagator.
+ * CAL_ERR_ARG without one, or when a value is not finite or outside [0, 1];
+ * then an earlier absorber stays as it was.  Replaces an earlier mask and
+ * clears the absorbed history (not the observables'); cal_prop_end and a new
+ * cal_prop_begin drop the absorber. */
+int cal_prop_set_absorber(cal_ctx* ctx, const double* mask);
+/* One row [t, absorbed] per completed step since the absorber was set, t as in
+ * cal_prop_get_observables.  A step that ends in CAL_WARN_BREAKDOWN leaves the
+ * state unmasked and records no row.  out == NULL: only *nrows.  Copies rows
+ * [first, first+count), two doubles each. */
+int cal_prop_get_absorbed(cal_ctx* ctx, int64_t first, int64_t count, double* out, int64_t* nrows);
+/* The masked kernel on host data, as cal_prop_combine_obs is for the
+ * observables: with ut, ub the two sums of row i as cal_prop_combine leaves
+ * them and m = mask[i] (n values, finite, in [0, 1]),
+ *   d = ut*ut;  d = d + ub*ub;  p = m*m;  g = 1.0 - p;  acc = acc + g*d
+ *   out_re[i] = m*ut;  out_im[i] = m*ub
+ * *norm2 and sums[nw + 2 nphi] (cal_prop_combine_obs's, either count may be 0)
+ * are those of out; *absorbed (may be NULL) = acc summed in the squared norm's
+ * fixed order. */
+int cal_prop_combine_masked(cal_ctx* ctx, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
+                            const double* mask, int nw, const double* W, int nphi, const double* phi_re,
+                            const double* phi_im, double* out_re, double* out_im, double* norm2, double* absorbed,
+                            double* sums);
+
 /* ---- a time-dependent potential H(t) = H0 + sum_k f_k(t) diag(W_k) ---- */
 /* W: n x nk column-major real diagonal operators, 0 <= nk <= 4, copied to the
  * device.  H0's diagonal V0 is taken from the context's matrix as it is at

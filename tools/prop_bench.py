@@ -22,7 +22,7 @@ each half bit for bit, and the norm drift over the run (unitarity).
 Prints one JSON line; --out also writes it to a file.
 
   python tools/prop_bench.py --windows 5 [--window-steps 4] [--observables NW,NPHI[,energy]]...
-                             [--copyback] [--combine-kernel] [--package-root DIR]
+                             [--absorber] [--copyback] [--combine-kernel] [--package-root DIR]
 
 The window mode (instead of 1.-5.): every leg is a fresh Propagator on one
 context, 2 warm-up steps, then --windows host-clock windows of --window-steps
@@ -36,10 +36,18 @@ and step; class "spmv" also with its launch count).  Legs:
                  state) reduced on the device inside the combine sweep;
   copyback_...   (--copyback) what that replaces: the same steps with
                  P.state() copied back after every step and the same sums
-                 done in NumPy.
+                 done in NumPy;
+  absorber       (--absorber) matrices.absorber_mask (width N/8) set with
+                 set_absorber: the mask applied and the absorbed norm summed
+                 inside the combine sweep;
+  copyback_absorber
+                 (--absorber --copyback) what that replaces: after every step
+                 the state is copied back, multiplied by the mask in NumPy and
+                 handed to a new Propagator.
 --combine-kernel adds the combine kernel alone with each --observables set
 through cal_prop_combine_obs, bytes (2n m + 2n + n NW + 2n NPHI) 8, next to
-the plain one.  --package-root imports ca_lanczos_amd from another checkout
+the plain one, and with --absorber the masked kernel alone through
+cal_prop_combine_masked, bytes (2n m + 3n) 8.  --package-root imports ca_lanczos_amd from another checkout
 (its built library), e.g. the parent commit's for an A/B in alternating
 fresh processes; such a checkout need not know the observables.
 """
@@ -73,6 +81,7 @@ def main():
     ap.add_argument("--window-steps", type=int, default=4)
     ap.add_argument("--observables", action="append", default=[], metavar="NW,NPHI[,energy]")
     ap.add_argument("--combine-kernel", action="store_true")
+    ap.add_argument("--absorber", action="store_true", help="window mode: also the leg with an absorbing mask set")
     ap.add_argument("--copyback", action="store_true", help="window mode: also the copy-back leg of every --observables")
     ap.add_argument("--package-root", default=None, help="import ca_lanczos_amd from this checkout")
     a = ap.parse_args()
@@ -288,6 +297,28 @@ def window_mode(cal, a, H, psi0, N, dim, res):
             norm2=abs(n2 - hist["norm2"][-1]) / n2, energy=abs(E - hist["energy"][-1]) / abs(E) if energy else None,
             W=float(np.max(np.abs(wv - hist["W"][-1]) / (np.abs(Wm).T @ np.abs(psi0) ** 2))) if nw else None,
             overlap=float(np.max(np.abs(ov - hist["overlap"][-1]))) / n2 if nphi else None)
+    mask = cal.matrices.absorber_mask((N,) * dim, max(N // 8, 1)) if a.absorber else None
+    if a.absorber:
+        legs["absorber"], _, _ = leg(lambda P: P.set_absorber(mask), None)
+        legs["absorber"]["expected_combine_bytes"] = (2.0 * n * a.s * a.blocks + 3.0 * n) * 8
+    if a.absorber and a.copyback:
+        # a new propagator per step: the state goes back, is masked in NumPy and uploaded again
+        def masked_steps(psi, k):
+            for _ in range(k):
+                P = cal.Propagator(H, psi, a.s, a.blocks, basis="newton", ctx=ctx)
+                P.step(a.dt, 1)
+                psi = mask * P.state()
+                P.close()
+            return psi
+
+        psi = masked_steps(psi0, 2)
+        ms = []
+        for _ in range(a.windows):
+            t0 = time.perf_counter()
+            psi = masked_steps(psi, a.window_steps)
+            ms.append(1e3 * (time.perf_counter() - t0) / a.window_steps)
+        legs["copyback_absorber"] = dict(ms_per_step=ms, norm2_left=float(np.sum(np.abs(psi) ** 2) /
+                                                                          np.sum(np.abs(psi0) ** 2)))
     res["legs"] = legs
 
     if a.combine_kernel:
@@ -315,6 +346,10 @@ def window_mode(cal, a, H, psi0, N, dim, res):
             r = timed(lambda: ctx.prop_combine_obs(Q, c, W, phi), base + (n * nw + 2.0 * n * nphi) * 8)
             r["expected_ms_from_byte_ratio"] = ck["plain"]["ms"] * r["expected_bytes"] / base
             ck["obs_%d_%d" % (nw, nphi)] = r
+        if a.absorber:
+            r = timed(lambda: ctx.prop_combine_masked(Q, c, mask), base + n * 8.0)
+            r["expected_ms_from_byte_ratio"] = ck["plain"]["ms"] * r["expected_bytes"] / base
+            ck["absorber"] = r
         res["combine_kernel"] = ck
     ctx.close()
 
