@@ -189,19 +189,42 @@ class Context:
         self.n = 2 * H.shape[0]
         return self
 
-    def prop_combine(self, Q, c):
-        """``nrm * Q_c * c`` on stacked halves (cal_prop_combine): Q is
-        2n x m real, c complex with m entries; returns (complex n-vector,
-        sum |out|^2 as the kernel's block partials reduce it)."""
+    def _prop_combine(self, Q, c, mask, W, phi, entry):
+        """The marshalling of the three host-data combine entries; ``entry``
+        names the one to call ("prop_combine": no observables, no mask;
+        "prop_combine_obs": no mask; "prop_combine_masked").  Returns (out,
+        norm2, absorbed, <W_k>, <phi_r|out>)."""
         Q = f64(Q)
         n, m = Q.shape[0] // 2, Q.shape[1]
         c = np.asarray(c, dtype=np.complex128).ravel()
         cre, cim = np.ascontiguousarray(c.real), np.ascontiguousarray(c.imag)
+        args = [self.h, n, m, ptr(Q), ptr(cre), ptr(cim)]
+        if entry == "prop_combine_masked":
+            mk = np.ascontiguousarray(mask, dtype=np.float64).ravel()
+            if mk.shape[0] != n:
+                raise ValueError("the mask needs n entries")
+            args.append(ptr(mk))
+        Wm, pre, pim = _obs_arrays(n, W, phi)
+        nw, nphi = Wm.shape[1], pre.shape[1]
         ore, oim = np.zeros(n), np.zeros(n)
-        n2 = ctypes.c_double()
-        check(self.h, lib.cal_prop_combine(self.h, n, m, ptr(Q), ptr(cre), ptr(cim), ptr(ore), ptr(oim),
-                                           ctypes.cast(ctypes.byref(n2), dp)), "prop_combine")
-        return ore + 1j * oim, n2.value
+        sums = np.zeros(max(nw + 2 * nphi, 1))
+        n2, ab = ctypes.c_double(), ctypes.c_double()
+        if entry != "prop_combine":
+            args += [nw, ptr(Wm) if nw else None, nphi, ptr(pre) if nphi else None, ptr(pim) if nphi else None]
+        args += [ptr(ore), ptr(oim), ctypes.cast(ctypes.byref(n2), dp)]
+        if entry == "prop_combine_masked":
+            args.append(ctypes.cast(ctypes.byref(ab), dp))
+        if entry != "prop_combine":
+            args.append(ptr(sums))
+        check(self.h, getattr(lib, "cal_" + entry)(*args), entry)
+        ov = sums[nw:nw + 2 * nphi]
+        return ore + 1j * oim, n2.value, ab.value, sums[:nw].copy(), ov[0::2] + 1j * ov[1::2]
+
+    def prop_combine(self, Q, c):
+        """``nrm * Q_c * c`` on stacked halves (cal_prop_combine): Q is
+        2n x m real, c complex with m entries; returns (complex n-vector,
+        sum |out|^2 as the kernel's block partials reduce it)."""
+        return self._prop_combine(Q, c, None, None, None, "prop_combine")[:2]
 
     def prop_combine_obs(self, Q, c, W=None, phi=None):
         """``prop_combine`` through the kernel that also reduces observables
@@ -209,21 +232,8 @@ class Context:
         phi complex reference states (a list or n x nphi), at most 4 each.
         Returns (out, norm2, <W_k> = sum W_k |out|^2 (nw), <phi_r|out> (nphi,
         complex)); out and norm2 have the bits of ``prop_combine``."""
-        Q = f64(Q)
-        n, m = Q.shape[0] // 2, Q.shape[1]
-        c = np.asarray(c, dtype=np.complex128).ravel()
-        cre, cim = np.ascontiguousarray(c.real), np.ascontiguousarray(c.imag)
-        Wm, pre, pim = _obs_arrays(n, W, phi)
-        nw, nphi = Wm.shape[1], pre.shape[1]
-        ore, oim = np.zeros(n), np.zeros(n)
-        sums = np.zeros(max(nw + 2 * nphi, 1))
-        n2 = ctypes.c_double()
-        check(self.h, lib.cal_prop_combine_obs(self.h, n, m, ptr(Q), ptr(cre), ptr(cim), nw, ptr(Wm) if nw else None,
-                                               nphi, ptr(pre) if nphi else None, ptr(pim) if nphi else None,
-                                               ptr(ore), ptr(oim), ctypes.cast(ctypes.byref(n2), dp), ptr(sums)),
-              "prop_combine_obs")
-        ov = sums[nw:nw + 2 * nphi]
-        return ore + 1j * oim, n2.value, sums[:nw].copy(), ov[0::2] + 1j * ov[1::2]
+        out, n2, _, wv, ov = self._prop_combine(Q, c, None, W, phi, "prop_combine_obs")
+        return out, n2, wv, ov
 
     def prop_combine_masked(self, Q, c, mask, W=None, phi=None):
         """``prop_combine_obs`` through the kernel that multiplies the result
@@ -231,25 +241,7 @@ class Context:
         with u = ``prop_combine(Q, c)``, out = mask * u.  Returns (out, norm2,
         absorbed = sum (1 - mask^2) |u|^2, <W_k>, <phi_r|out>); norm2 and the
         observables are those of out."""
-        Q = f64(Q)
-        n, m = Q.shape[0] // 2, Q.shape[1]
-        c = np.asarray(c, dtype=np.complex128).ravel()
-        cre, cim = np.ascontiguousarray(c.real), np.ascontiguousarray(c.imag)
-        mk = np.ascontiguousarray(mask, dtype=np.float64).ravel()
-        if mk.shape[0] != n:
-            raise ValueError("the mask needs n entries")
-        Wm, pre, pim = _obs_arrays(n, W, phi)
-        nw, nphi = Wm.shape[1], pre.shape[1]
-        ore, oim = np.zeros(n), np.zeros(n)
-        sums = np.zeros(max(nw + 2 * nphi, 1))
-        n2, ab = ctypes.c_double(), ctypes.c_double()
-        check(self.h, lib.cal_prop_combine_masked(self.h, n, m, ptr(Q), ptr(cre), ptr(cim), ptr(mk), nw,
-                                                  ptr(Wm) if nw else None, nphi, ptr(pre) if nphi else None,
-                                                  ptr(pim) if nphi else None, ptr(ore), ptr(oim),
-                                                  ctypes.cast(ctypes.byref(n2), dp), ctypes.cast(ctypes.byref(ab), dp),
-                                                  ptr(sums)), "prop_combine_masked")
-        ov = sums[nw:nw + 2 * nphi]
-        return ore + 1j * oim, n2.value, ab.value, sums[:nw].copy(), ov[0::2] + 1j * ov[1::2]
+        return self._prop_combine(Q, c, mask, W, phi, "prop_combine_masked")
 
     def set_diagonal(self, d):
         """Rewrite the stored diagonal of the resident matrix in place

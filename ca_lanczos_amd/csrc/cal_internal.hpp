@@ -519,21 +519,27 @@ hipError_t launch_fold_down(const ColList& P, const OutList& Q, const FoldArgs& 
 // m device coefficients (Re / Im of nrm * expm(-i dt T) e_1):
 //   out[i]     = sum_j Q[i,j] a_j - Q[i+n,j] b_j
 //   out[i + n] = sum_j Q[i,j] b_j + Q[i+n,j] a_j      (0 <= i < n)
-// in the fixed order of DESIGN.md (one chain per output row, j ascending) and
-// partial[block] = the block's sum of out^2 (prop_combine_blocks(n) blocks;
-// launch_reduce gives the next step's squared norm).  m <= kPropMaxCols.
+// in the fixed order of DESIGN.md (one chain per output row, j ascending),
+// m <= kPropMaxCols.  The same sweep optionally
+//   - multiplies by an absorbing mask (mask non-null; k_prop_combine's ABS
+//     flag): with u the row's two sums, out = mask .* u is stored, and the
+//     squared norm and the observables below are those of out.  mask: n
+//     doubles, 16-byte aligned, in an allocation of an even ldm >= n doubles
+//     (the pad is not read);
+//   - reduces observables of out (obs.nw + obs.np > 0; the OBS flag): nw <=
+//     kPropMaxObs real diagonal operators W(:, k) and np <= kPropMaxObs
+//     reference states pr(:, r) + i pi(:, r), column-major with the even
+//     leading dimension obs.ld >= n and 16-byte-aligned origins.
+// Neither changes the bits of out (before the mask) or of the squared norm's
+// chain.  The sweep leaves prop_combine_quantities(p) quantities, quantity
+// q's block partials at partial[q * blocks + block], blocks =
+// prop_combine_blocks(n) (launch_reduce(partial, blocks, quantities, ...)
+// sums them all, the next step's squared norm first), in the order
+//   q = 0                      sum out^2
+//   1 + k        (k < nw)      sum W_k |out|^2
+//   1 + nw + 2r, + 2r + 1      Re and Im <phi_r|out>   (r < np)
+//   1 + nw + 2 np  (mask set)  sum (1 - mask^2) |u|^2
 constexpr int kPropMaxCols = 512;
-int prop_combine_blocks(int64_t n);
-hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                               double* out, double* partial, hipStream_t st);
-// The same sweep with observables of the new state (k_prop_combine's OBS
-// flag): nw <= kPropMaxObs real diagonal operators W(:, k) and np <=
-// kPropMaxObs reference states pr(:, r) + i pi(:, r), column-major with the
-// even leading dimension ld >= n and 16-byte-aligned origins.  Quantity q's
-// block partials are partial[q * blocks + block], blocks =
-// prop_combine_blocks(n) (launch_reduce(partial, blocks, 1 + nw + 2 np, ...)
-// sums them all): q = 0 the squared norm (the bits of launch_prop_combine),
-// 1 + k sum W_k |psi'|^2, 1 + nw + 2r and + 2r + 1 Re and Im <phi_r|psi'>.
 constexpr int kPropMaxObs = 4;
 struct PropObs {
     const double* W = nullptr;
@@ -542,17 +548,21 @@ struct PropObs {
     int64_t ld = 0;
     int nw = 0, np = 0;
 };
-hipError_t launch_prop_combine_obs(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                                   double* out, double* partial, const PropObs& o, hipStream_t st);
-// The same sweep under an absorbing mask (k_prop_combine's ABS flag): with u
-// the row's two sums, out = mask .* u is stored, the squared norm and the
-// observables are those of out, and one more quantity, index 1 + nw + 2 np
-// (launch_reduce over 2 + nw + 2 np), is sum (1 - mask^2) |u|^2.  mask: n
-// doubles, 16-byte aligned, in an allocation of an even ldm >= n doubles (the
-// pad is not read).  o.nw = o.np = 0 takes the kernels without observables.
-hipError_t launch_prop_combine_masked(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                                      double* out, double* partial, const PropObs& o, const double* mask,
-                                      int64_t ldm, hipStream_t st);
+struct PropCombine {
+    const double* Q = nullptr;
+    int64_t ld = 0, n = 0;
+    int m = 0;
+    const double* a = nullptr;
+    const double* b = nullptr;
+    double* out = nullptr;
+    double* partial = nullptr;
+    PropObs obs;                   // zero counts: none
+    const double* mask = nullptr;  // null: none
+    int64_t ldm = 0;
+};
+int prop_combine_blocks(int64_t n);
+int prop_combine_quantities(const PropCombine& p);
+hipError_t launch_prop_combine(const PropCombine& p, hipStream_t st);
 
 // ---- the time-dependent diagonal H(t) = H0 + sum_k f_k(t) diag(W_k) (prop.hip) ----
 // k_diag_find: dpos[r] = the position in val of row r's first entry with

@@ -78,6 +78,12 @@ struct PropState {
     bool obs_on() const { return nw > 0 || nphi > 0 || energy; }
     bool abs_on() const { return d_mask != nullptr; }
     int nq() const { return nw + 2 * nphi; }
+    // what a step reduces, in the order combine_dev leaves it in d_red and in
+    // h_coef + 2 kPropMaxCols: [psi'psi, the nq sums, the absorbed norm
+    // (absorber on), the energy (energy on)]
+    int red_absorbed() const { return 1 + nq(); }
+    int red_energy() const { return 1 + nq() + (abs_on() ? 1 : 0); }
+    int red_count() const { return red_energy() + (energy ? 1 : 0); }
     double* psi(const cal_ctx* c) const { return d_psi + c->A.lpad; }
 };
 
@@ -85,6 +91,46 @@ namespace {
 
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+int64_t pad64(int64_t n) { return ((n + 63) / 64) * 64; }
+
+PropObs make_obs(const double* base, int64_t ldo, int nw, int nphi) {
+    PropObs o;
+    o.W = base;
+    o.pr = base + (size_t)nw * ldo;
+    o.pi = base + (size_t)(nw + nphi) * ldo;
+    o.ld = ldo;
+    o.nw = nw;
+    o.np = nphi;
+    return o;
+}
+
+// 0 with a propagator open on c (and, need_matrix, the matrix it was begun on still set)
+int active_prop(cal_ctx* c, const std::string& who, bool need_matrix) {
+    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, who + ": no active propagator");
+    if (need_matrix && (!c->has_A || c->A.n_local != 2 * c->prop->n))
+        return set_error(c, CAL_ERR_ARG, who + ": the context's matrix changed since cal_prop_begin");
+    return 0;
+}
+
+// k host columns of n doubles as columns of ld doubles at dst, the pad rows
+// zero (src null: all zeros); on the stream
+int upload_cols(cal_ctx* c, double* dst, int64_t ld, const double* src, int64_t n, int k) {
+    if (k < 1) return 0;
+    CAL_HIP(c, hipMemsetAsync(dst, 0, (size_t)k * ld * sizeof(double), c->stream));
+    if (src)
+        CAL_HIP(c, hipMemcpy2DAsync(dst, ld * sizeof(double), src, n * sizeof(double), n * sizeof(double), k,
+                                    hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// W, phi_re and phi_im (null: zeros) as columns of ldo doubles at dst, on the stream
+int upload_obs(cal_ctx* c, double* dst, int64_t ldo, int64_t n, int nw, const double* W, int nphi,
+               const double* phi_re, const double* phi_im) {
+    CAL_TRY(upload_cols(c, dst, ldo, W, n, nw));
+    CAL_TRY(upload_cols(c, dst + (size_t)nw * ldo, ldo, phi_re, n, nphi));
+    return upload_cols(c, dst + (size_t)(nw + nphi) * ldo, ldo, phi_im, n, nphi);
 }
 
 void obs_free(PropState& P) {
@@ -138,48 +184,29 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     std::memcpy(P.h_coef + kPropMaxCols, b, m * sizeof(double));
     CAL_HIP_OTHER(c, hipMemcpyAsync(P.d_coef, P.h_coef, 2 * kPropMaxCols * sizeof(double), hipMemcpyHostToDevice,
                                     c->stream));
+    PropCombine k;
+    k.Q = Q;
+    k.ld = ld;
+    k.n = P.n;
+    k.m = m;
+    k.a = P.d_coef;
+    k.b = P.d_coef + kPropMaxCols;
+    k.out = P.psi(c);
+    k.obs = make_obs(P.d_obs, P.ldo, P.nw, P.nphi);
+    k.mask = P.d_mask;
+    k.ldm = P.ldm;
     const int nb = prop_combine_blocks(P.n);
-    const int na = P.abs_on() ? 1 : 0;
-    if (!P.obs_on() && !na) {
-        CAL_TRY(ensure_partial(c, nb));
-        CAL_TRY(ensure_red(c, 1));
-        const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n) * 8.0);
-        const hipError_t e =
-            launch_prop_combine(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c), c->d_partial, c->stream);
-        timer_end(c, t);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
-        CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1, c->d_red, c->stream));
-        CAL_HIP_OTHER(c, hipMemcpyAsync(P.h_coef + 2 * kPropMaxCols, c->d_red, sizeof(double), hipMemcpyDeviceToHost,
-                                        c->stream));
-        CAL_HIP(c, hipStreamSynchronize(c->stream));
-        P.nrm2 = P.h_coef[2 * kPropMaxCols];
-        return 0;
-    }
-    // with observables or an absorber: d_red = [psi'psi, the nw + 2 nphi sums,
-    // the absorbed norm (absorber on), the energy], fetched with the squared
-    // norm in the one pinned transfer
-    const int nq = P.nq();
+    const int nk = prop_combine_quantities(k);
     const int nd = dot_blocks(2 * P.n);
-    const size_t pe = (size_t)(1 + nq + na) * nb;  // the energy's partials follow the combine's
-    CAL_TRY(ensure_partial(c, pe + (size_t)std::max(P.eparts, nd)));
-    CAL_TRY(ensure_red(c, (size_t)nq + na + 2));
-    PropObs o;
-    o.W = P.d_obs;
-    o.pr = P.d_obs + (size_t)P.nw * P.ldo;
-    o.pi = P.d_obs + (size_t)(P.nw + P.nphi) * P.ldo;
-    o.ld = P.ldo;
-    o.nw = P.nw;
-    o.np = P.nphi;
-    const int t = timer_begin(
-        c, 2, ((double)2 * P.n * m + (double)2 * P.n + (double)P.n * (P.nw + 2 * P.nphi) + (double)P.n * na) * 8.0);
-    const hipError_t e =
-        na ? launch_prop_combine_masked(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c), c->d_partial, o,
-                                        P.d_mask, P.ldm, c->stream)
-           : launch_prop_combine_obs(Q, ld, P.n, m, P.d_coef, P.d_coef + kPropMaxCols, P.psi(c), c->d_partial, o,
-                                     c->stream);
+    const size_t pe = (size_t)nk * nb;  // the energy's partials follow the combine's
+    CAL_TRY(ensure_partial(c, pe + (P.energy ? (size_t)std::max(P.eparts, nd) : 0)));
+    CAL_TRY(ensure_red(c, (size_t)P.red_count()));
+    k.partial = c->d_partial;
+    const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n + (double)P.n * (nk - 1)) * 8.0);
+    const hipError_t e = launch_prop_combine(k, c->stream);
     timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, na ? "launch_prop_combine_masked" : "launch_prop_combine_obs");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1 + nq + na, c->d_red, c->stream));
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, nk, c->d_red, c->stream));
     if (P.energy) {
         // <psi'|H|psi'> = y'x over the stacked rows, y = blkdiag(H, H) x: the
         // fused Lanczos mode's dot, reduced as lanczos_std.cpp reduces it
@@ -187,16 +214,17 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
         double* part = c->d_partial + pe;
         if (P.eparts > 0) {
             CAL_TRY(spmv_lanczos_dev(c, P.psi(c), nullptr, nullptr, y, part));
-            CAL_HIP_OTHER(c, launch_reduce(part, P.eparts, 1, c->d_red + 1 + nq + na, c->stream));
+            CAL_HIP_OTHER(c, launch_reduce(part, P.eparts, 1, c->d_red + P.red_energy(), c->stream));
         } else {
             CAL_TRY(spmv_dev(c, P.psi(c), y, 0, 0.0, 0.0, nullptr));
             CAL_HIP_OTHER(c, launch_dot(y, P.psi(c), 2 * P.n, part, nd, c->stream));
-            CAL_HIP_OTHER(c, launch_reduce(part, nd, 1, c->d_red + 1 + nq + na, c->stream));
+            CAL_HIP_OTHER(c, launch_reduce(part, nd, 1, c->d_red + P.red_energy(), c->stream));
         }
     }
+    // everything reduced comes back with the squared norm in the one pinned transfer
     double* h = P.h_coef + 2 * kPropMaxCols;
-    CAL_HIP_OTHER(c, hipMemcpyAsync(h, c->d_red, (size_t)(nq + na + (P.energy ? 2 : 1)) * sizeof(double),
-                                    hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP_OTHER(c, hipMemcpyAsync(h, c->d_red, (size_t)P.red_count() * sizeof(double), hipMemcpyDeviceToHost,
+                                    c->stream));
     CAL_HIP(c, hipStreamSynchronize(c->stream));
     P.nrm2 = h[0];
     return 0;
@@ -205,17 +233,16 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
 // the history row of the step just completed (combine_dev's transfer is in h_coef)
 void record_row(PropState& P) {
     const double* h = P.h_coef + 2 * kPropMaxCols;
-    const int nq = P.nq();
     P.hist.push_back(P.t);
     P.hist.push_back(h[0]);
-    P.hist.push_back(P.energy ? h[1 + nq + (P.abs_on() ? 1 : 0)] : std::numeric_limits<double>::quiet_NaN());
-    P.hist.insert(P.hist.end(), h + 1, h + 1 + nq);
+    P.hist.push_back(P.energy ? h[P.red_energy()] : std::numeric_limits<double>::quiet_NaN());
+    P.hist.insert(P.hist.end(), h + 1, h + 1 + P.nq());
 }
 
 // the absorber's row [t, absorbed] of the step just completed
 void record_absorbed(PropState& P) {
     P.ahist.push_back(P.t);
-    P.ahist.push_back(P.h_coef[2 * kPropMaxCols + 1 + P.nq()]);
+    P.ahist.push_back(P.h_coef[2 * kPropMaxCols + P.red_absorbed()]);
 }
 
 // One Krylov build from the current state: CA blocks until max_blocks, the
@@ -291,6 +318,74 @@ int check_prop_args(cal_ctx* c, int64_t n, int s, int max_blocks, const char* ba
     return 0;
 }
 
+bool combine_args_ok(int64_t n, int m, const double* Q, const double* c_re, const double* c_im, const double* out_re,
+                     const double* out_im) {
+    return n >= 1 && m >= 1 && m <= kPropMaxCols && Q && c_re && c_im && out_re && out_im;
+}
+
+bool obs_counts_ok(int nw, const double* W, int nphi, const double* phi_re) {
+    return nw >= 0 && nw <= kPropMaxObs && nphi >= 0 && nphi <= kPropMaxObs && (nw == 0 || W) && (nphi == 0 || phi_re);
+}
+
+// every value finite and in [0, 1] (NaN fails both comparisons)
+bool mask_ok(const double* mask, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(mask[i] >= 0.0 && mask[i] <= 1.0)) return false;
+    return true;
+}
+
+// The combine sweep on host data, behind the cal_prop_combine* exports (which
+// check the arguments): mask null for none, nw = nphi = 0 for no observables.
+// d_scratch holds [Q (ld x m) | out (ld) | W and phi (ldo x nq) | the mask
+// (ldo, when given) | the coefficients (2 m)], ld and ldo multiples of 64, so
+// every origin is 16-byte aligned.
+int combine_host(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
+                 const double* mask, int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
+                 double* out_re, double* out_im, double* norm2, double* absorbed, double* sums) {
+    const int nq = nw + 2 * nphi, na = mask ? 1 : 0;
+    const int64_t ld = pad64(2 * n), ldo = pad64(n);
+    CAL_TRY(ensure_scratch(c, (size_t)ld * (m + 1) + (size_t)ldo * (nq + na) + 2 * (size_t)m));
+    double* dobs = c->d_scratch + (size_t)ld * (m + 1);
+    double* dmask = dobs + (size_t)ldo * nq;
+    double* dco = dmask + (size_t)ldo * na;
+    PropCombine k;
+    k.Q = c->d_scratch;
+    k.ld = ld;
+    k.n = n;
+    k.m = m;
+    k.a = dco;
+    k.b = dco + m;
+    k.out = c->d_scratch + (size_t)ld * m;
+    k.obs = make_obs(dobs, ldo, nw, nphi);
+    k.mask = mask ? dmask : nullptr;
+    k.ldm = ldo;
+    const int nb = prop_combine_blocks(n);
+    const int nk = prop_combine_quantities(k);
+    CAL_TRY(ensure_partial(c, (size_t)nk * nb));
+    CAL_TRY(ensure_red(c, (size_t)nk));
+    k.partial = c->d_partial;
+    CAL_HIP(c, hipMemcpy2DAsync(c->d_scratch, ld * sizeof(double), Q, 2 * n * sizeof(double), 2 * n * sizeof(double),
+                                m, hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco, c_re, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (mask) CAL_HIP(c, hipMemcpyAsync(dmask, mask, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_TRY(upload_obs(c, dobs, ldo, n, nw, W, nphi, phi_re, phi_im));
+    const int t = timer_begin(c, 2, ((double)2 * n * m + (double)2 * n + (double)n * (nk - 1)) * 8.0);
+    const hipError_t e = launch_prop_combine(k, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, nk, c->d_red, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out_re, k.out, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out_im, k.out + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    double red[2 + 3 * kPropMaxObs] = {0.0};
+    CAL_HIP(c, hipMemcpyAsync(red, c->d_red, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    if (norm2) *norm2 = red[0];
+    for (int q = 0; q < nq; ++q) sums[q] = red[1 + q];
+    if (mask && absorbed) *absorbed = red[1 + nq];
+    return 0;
+}
+
 }  // namespace
 }  // namespace cal
 
@@ -328,55 +423,10 @@ int cal_prop_combine(cal_ctx* c, int64_t n, int m, const double* Q, const double
                      double* out_re, double* out_im, double* norm2) {
     if (!c) return CAL_ERR_ARG;
     hipSetDevice(c->device);
-    if (n < 1 || m < 1 || m > kPropMaxCols || !Q || !c_re || !c_im || !out_re || !out_im)
+    if (!combine_args_ok(n, m, Q, c_re, c_im, out_re, out_im))
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine: need n >= 1, 1 <= m <= 512 and non-null arrays");
-    const int64_t ld = ((2 * n + 63) / 64) * 64;
-    const int nb = prop_combine_blocks(n);
-    // Q (ld x m), out (ld), the coefficients (2 m)
-    CAL_TRY(ensure_scratch(c, (size_t)ld * (m + 1) + 2 * (size_t)m));
-    CAL_TRY(ensure_partial(c, nb));
-    CAL_TRY(ensure_red(c, 1));
-    double* dQ = c->d_scratch;
-    double* dout = dQ + (size_t)ld * m;
-    double* dco = dout + ld;
-    CAL_HIP(c, hipMemcpy2DAsync(dQ, ld * sizeof(double), Q, 2 * n * sizeof(double), 2 * n * sizeof(double), m,
-                                hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dco, c_re, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const int t = timer_begin(c, 2, ((double)2 * n * m + (double)2 * n) * 8.0);
-    const hipError_t e = launch_prop_combine(dQ, ld, n, m, dco, dco + m, dout, c->d_partial, c->stream);
-    timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1, c->d_red, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out_re, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out_im, dout + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    double nn = 0.0;
-    CAL_HIP(c, hipMemcpyAsync(&nn, c->d_red, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CAL_HIP(c, hipStreamSynchronize(c->stream));
-    if (norm2) *norm2 = nn;
-    return 0;
-}
-
-// W, phi_re and phi_im (null: zeros) as columns of ldo doubles at dst, on the stream
-static int upload_obs(cal_ctx* c, double* dst, int64_t ldo, int64_t n, int nw, const double* W, int nphi,
-                      const double* phi_re, const double* phi_im) {
-    const size_t cols = (size_t)nw + 2 * (size_t)nphi;
-    if (cols == 0) return 0;
-    CAL_HIP(c, hipMemsetAsync(dst, 0, cols * ldo * sizeof(double), c->stream));
-    auto put = [&](double* d, const double* src, int k) -> int {
-        if (k > 0 && src)
-            CAL_HIP(c, hipMemcpy2DAsync(d, ldo * sizeof(double), src, n * sizeof(double), n * sizeof(double), k,
-                                        hipMemcpyHostToDevice, c->stream));
-        return 0;
-    };
-    CAL_TRY(put(dst, W, nw));
-    CAL_TRY(put(dst + (size_t)nw * ldo, phi_re, nphi));
-    CAL_TRY(put(dst + (size_t)(nw + nphi) * ldo, phi_im, nphi));
-    return 0;
-}
-
-static bool obs_counts_ok(int nw, const double* W, int nphi, const double* phi_re) {
-    return nw >= 0 && nw <= kPropMaxObs && nphi >= 0 && nphi <= kPropMaxObs && (nw == 0 || W) && (nphi == 0 || phi_re);
+    return combine_host(c, n, m, Q, c_re, c_im, nullptr, 0, nullptr, 0, nullptr, nullptr, out_re, out_im, norm2,
+                        nullptr, nullptr);
 }
 
 int cal_prop_combine_obs(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
@@ -384,63 +434,26 @@ int cal_prop_combine_obs(cal_ctx* c, int64_t n, int m, const double* Q, const do
                          double* out_re, double* out_im, double* norm2, double* sums) {
     if (!c) return CAL_ERR_ARG;
     hipSetDevice(c->device);
-    if (n < 1 || m < 1 || m > kPropMaxCols || !Q || !c_re || !c_im || !out_re || !out_im)
+    if (!combine_args_ok(n, m, Q, c_re, c_im, out_re, out_im))
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine_obs: need n >= 1, 1 <= m <= 512 and non-null arrays");
-    const int nq = nw + 2 * nphi;
-    if (!obs_counts_ok(nw, W, nphi, phi_re) || (nq > 0 && !sums))
+    if (!obs_counts_ok(nw, W, nphi, phi_re) || (nw + 2 * nphi > 0 && !sums))
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine_obs: need 0 <= nw, nphi <= 4 with their arrays and sums");
-    const int64_t ld = ((2 * n + 63) / 64) * 64;
-    const int64_t ldo = ((n + 63) / 64) * 64;
-    const int nb = prop_combine_blocks(n);
-    // Q (ld x m), out (ld), W and phi (ldo x nq), the coefficients (2 m)
-    CAL_TRY(ensure_scratch(c, (size_t)ld * (m + 1) + (size_t)ldo * nq + 2 * (size_t)m));
-    CAL_TRY(ensure_partial(c, (size_t)(1 + nq) * nb));
-    CAL_TRY(ensure_red(c, (size_t)nq + 1));
-    double* dQ = c->d_scratch;
-    double* dout = dQ + (size_t)ld * m;
-    double* dobs = dout + ld;
-    double* dco = dobs + (size_t)ldo * nq;
-    CAL_HIP(c, hipMemcpy2DAsync(dQ, ld * sizeof(double), Q, 2 * n * sizeof(double), 2 * n * sizeof(double), m,
-                                hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dco, c_re, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_TRY(upload_obs(c, dobs, ldo, n, nw, W, nphi, phi_re, phi_im));
-    PropObs o;
-    o.W = dobs;
-    o.pr = dobs + (size_t)nw * ldo;
-    o.pi = dobs + (size_t)(nw + nphi) * ldo;
-    o.ld = ldo;
-    o.nw = nw;
-    o.np = nphi;
-    const int t = timer_begin(c, 2, ((double)2 * n * m + (double)2 * n + (double)n * nq) * 8.0);
-    const hipError_t e = launch_prop_combine_obs(dQ, ld, n, m, dco, dco + m, dout, c->d_partial, o, c->stream);
-    timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine_obs");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1 + nq, c->d_red, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out_re, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out_im, dout + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    double red[1 + 3 * kPropMaxObs] = {0.0};
-    CAL_HIP(c, hipMemcpyAsync(red, c->d_red, (size_t)(1 + nq) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CAL_HIP(c, hipStreamSynchronize(c->stream));
-    if (norm2) *norm2 = red[0];
-    for (int q = 0; q < nq; ++q) sums[q] = red[1 + q];
-    return 0;
+    return combine_host(c, n, m, Q, c_re, c_im, nullptr, nw, W, nphi, phi_re, phi_im, out_re, out_im, norm2, nullptr,
+                        sums);
 }
 
 int cal_prop_set_observables(cal_ctx* c, int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
                              int energy) {
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_set_observables: no active propagator");
+    CAL_TRY(active_prop(c, "cal_prop_set_observables", true));
     hipSetDevice(c->device);
     PropState& P = *c->prop;
     if (!obs_counts_ok(nw, W, nphi, phi_re))
         return set_error(c, CAL_ERR_ARG, "cal_prop_set_observables: need 0 <= nw, nphi <= 4 with their arrays");
-    if (!c->has_A || c->A.n_local != 2 * P.n)
-        return set_error(c, CAL_ERR_ARG, "cal_prop_set_observables: the context's matrix changed since cal_prop_begin");
     CAL_HIP(c, hipStreamSynchronize(c->stream));
     obs_free(P);
     const int nq = nw + 2 * nphi;
     if (nq > 0) {
-        P.ldo = ((P.n + 63) / 64) * 64;
+        P.ldo = pad64(P.n);
         CAL_HIP(c, hipMalloc((void**)&P.d_obs, (size_t)nq * P.ldo * sizeof(double)));
         const int st = upload_obs(c, P.d_obs, P.ldo, P.n, nw, W, nphi, phi_re, phi_im);
         if (st < 0 || hipStreamSynchronize(c->stream) != hipSuccess) {  // the sources are the caller's
@@ -461,7 +474,7 @@ int cal_prop_set_observables(cal_ctx* c, int nw, const double* W, int nphi, cons
 }
 
 int cal_prop_get_observables(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows, int* ncols) {
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_get_observables: no active propagator");
+    CAL_TRY(active_prop(c, "cal_prop_get_observables", false));
     const PropState& P = *c->prop;
     const int nc = 3 + P.nq();
     const int64_t nr = (int64_t)(P.hist.size() / nc);
@@ -474,71 +487,25 @@ int cal_prop_get_observables(cal_ctx* c, int64_t first, int64_t count, double* o
     return 0;
 }
 
-// every value finite and in [0, 1] (NaN fails both comparisons)
-static bool mask_ok(const double* mask, int64_t n) {
-    for (int64_t i = 0; i < n; ++i)
-        if (!(mask[i] >= 0.0 && mask[i] <= 1.0)) return false;
-    return true;
-}
-
 int cal_prop_combine_masked(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
                             const double* mask, int nw, const double* W, int nphi, const double* phi_re,
                             const double* phi_im, double* out_re, double* out_im, double* norm2, double* absorbed,
                             double* sums) {
     if (!c) return CAL_ERR_ARG;
     hipSetDevice(c->device);
-    if (n < 1 || m < 1 || m > kPropMaxCols || !Q || !c_re || !c_im || !mask || !out_re || !out_im)
+    if (!combine_args_ok(n, m, Q, c_re, c_im, out_re, out_im) || !mask)
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine_masked: need n >= 1, 1 <= m <= 512 and non-null arrays");
-    const int nq = nw + 2 * nphi;
-    if (!obs_counts_ok(nw, W, nphi, phi_re) || (nq > 0 && !sums))
+    if (!obs_counts_ok(nw, W, nphi, phi_re) || (nw + 2 * nphi > 0 && !sums))
         return set_error(c, CAL_ERR_ARG,
                          "cal_prop_combine_masked: need 0 <= nw, nphi <= 4 with their arrays and sums");
     if (!mask_ok(mask, n))
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine_masked: the mask must be finite and within [0, 1]");
-    const int64_t ld = ((2 * n + 63) / 64) * 64;
-    const int64_t ldo = ((n + 63) / 64) * 64;
-    const int nb = prop_combine_blocks(n);
-    // Q (ld x m), out (ld), W and phi (ldo x nq), the mask (ldo), the coefficients (2 m)
-    CAL_TRY(ensure_scratch(c, (size_t)ld * (m + 1) + (size_t)ldo * (nq + 1) + 2 * (size_t)m));
-    CAL_TRY(ensure_partial(c, (size_t)(2 + nq) * nb));
-    CAL_TRY(ensure_red(c, (size_t)nq + 2));
-    double* dQ = c->d_scratch;
-    double* dout = dQ + (size_t)ld * m;
-    double* dobs = dout + ld;
-    double* dmask = dobs + (size_t)ldo * nq;
-    double* dco = dmask + ldo;
-    CAL_HIP(c, hipMemcpy2DAsync(dQ, ld * sizeof(double), Q, 2 * n * sizeof(double), 2 * n * sizeof(double), m,
-                                hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dco, c_re, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dmask, mask, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_TRY(upload_obs(c, dobs, ldo, n, nw, W, nphi, phi_re, phi_im));
-    PropObs o;
-    o.W = dobs;
-    o.pr = dobs + (size_t)nw * ldo;
-    o.pi = dobs + (size_t)(nw + nphi) * ldo;
-    o.ld = ldo;
-    o.nw = nw;
-    o.np = nphi;
-    const int t = timer_begin(c, 2, ((double)2 * n * m + (double)2 * n + (double)n * nq + (double)n) * 8.0);
-    const hipError_t e =
-        launch_prop_combine_masked(dQ, ld, n, m, dco, dco + m, dout, c->d_partial, o, dmask, ldo, c->stream);
-    timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine_masked");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 2 + nq, c->d_red, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out_re, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out_im, dout + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    double red[2 + 3 * kPropMaxObs] = {0.0};
-    CAL_HIP(c, hipMemcpyAsync(red, c->d_red, (size_t)(2 + nq) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CAL_HIP(c, hipStreamSynchronize(c->stream));
-    if (norm2) *norm2 = red[0];
-    for (int q = 0; q < nq; ++q) sums[q] = red[1 + q];
-    if (absorbed) *absorbed = red[1 + nq];
-    return 0;
+    return combine_host(c, n, m, Q, c_re, c_im, mask, nw, W, nphi, phi_re, phi_im, out_re, out_im, norm2, absorbed,
+                        sums);
 }
 
 int cal_prop_set_absorber(cal_ctx* c, const double* mask) {
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_set_absorber: no active propagator");
+    CAL_TRY(active_prop(c, "cal_prop_set_absorber", false));
     hipSetDevice(c->device);
     PropState& P = *c->prop;
     if (mask && !mask_ok(mask, P.n))
@@ -549,11 +516,10 @@ int cal_prop_set_absorber(cal_ctx* c, const double* mask) {
         return 0;
     }
     // the new copy first: a failure leaves an earlier absorber as it was
-    const int64_t ldm = ((P.n + 63) / 64) * 64;
+    const int64_t ldm = pad64(P.n);
     double* d = nullptr;
     CAL_HIP(c, hipMalloc((void**)&d, ldm * sizeof(double)));
-    if (hipMemsetAsync(d, 0, ldm * sizeof(double), c->stream) != hipSuccess ||
-        hipMemcpyAsync(d, mask, P.n * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+    if (upload_cols(c, d, ldm, mask, P.n, 1) < 0 ||
         hipStreamSynchronize(c->stream) != hipSuccess) {  // the source is the caller's
         hipFree(d);
         return set_error(c, CAL_ERR_HIP, "cal_prop_set_absorber: upload failed");
@@ -565,7 +531,7 @@ int cal_prop_set_absorber(cal_ctx* c, const double* mask) {
 }
 
 int cal_prop_get_absorbed(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows) {
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_get_absorbed: no active propagator");
+    CAL_TRY(active_prop(c, "cal_prop_get_absorbed", false));
     const PropState& P = *c->prop;
     const int64_t nr = (int64_t)(P.ahist.size() / 2);
     if (nrows) *nrows = nr;
@@ -642,13 +608,11 @@ int cal_prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* ps
 static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int adaptive, int nsteps, const double* f,
                       int ldf) {
     const std::string w = who;
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, w + ": no active propagator");
+    CAL_TRY(active_prop(c, w, true));
     hipSetDevice(c->device);
     PropState& P = *c->prop;
     if (!std::isfinite(dt) || nsteps < 0 || std::isnan(tol))
         return set_error(c, CAL_ERR_ARG, w + ": need a finite dt, a tol and nsteps >= 0");
-    if (!c->has_A || c->A.n_local != 2 * P.n)
-        return set_error(c, CAL_ERR_ARG, w + ": the context's matrix changed since cal_prop_begin");
     if (f) {
         if (P.nk < 1 || !P.d_v0) return set_error(c, CAL_ERR_ARG, w + ": no drive set (cal_prop_set_drive)");
         if (c->A_gen != P.drv_gen)
@@ -710,29 +674,23 @@ int cal_prop_step_driven(cal_ctx* c, double dt, double tol, int adaptive, int ns
 }
 
 int cal_prop_set_drive(cal_ctx* c, int nk, const double* W) {
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: no active propagator");
+    CAL_TRY(active_prop(c, "cal_prop_set_drive", true));
     hipSetDevice(c->device);
     PropState& P = *c->prop;
     if (nk < 0 || nk > kDriveMaxOps || (nk > 0 && !W))
         return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: need 0 <= nk <= 4 and W (n x nk) when nk > 0");
-    if (!c->has_A || c->A.n_local != 2 * P.n)
-        return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: the context's matrix changed since cal_prop_begin");
     for (size_t i = 0; i < (size_t)nk * P.n; ++i)
         if (!std::isfinite(W[i])) return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: non-finite entry in W");
     CAL_TRY(diag_positions(c));  // refusals leave the matrix and an earlier drive as they are
     CAL_TRY(drive_off(c, P));    // an earlier drive: its V0 goes back first
     if (nk == 0) return 0;
-    P.ldd = ((P.n + 63) / 64) * 64;
+    P.ldd = pad64(P.n);
     P.drv_gen = c->A_gen;
     CAL_HIP(c, hipMalloc((void**)&P.d_v0, P.n * sizeof(double)));
     CAL_HIP(c, hipMalloc((void**)&P.d_drv, (size_t)nk * P.ldd * sizeof(double)));
     int st = diag_gather_dev(c, P.d_v0, P.n);
-    if (st == 0 && hipMemsetAsync(P.d_drv, 0, (size_t)nk * P.ldd * sizeof(double), c->stream) != hipSuccess)
-        st = set_error(c, CAL_ERR_HIP, "cal_prop_set_drive: memset failed");
-    if (st == 0 && hipMemcpy2DAsync(P.d_drv, P.ldd * sizeof(double), W, P.n * sizeof(double), P.n * sizeof(double), nk,
-                                    hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        st = set_error(c, CAL_ERR_HIP, "cal_prop_set_drive: upload failed");
-    if (st == 0 && hipStreamSynchronize(c->stream) != hipSuccess)  // W is the caller's
+    if (st == 0 && (upload_cols(c, P.d_drv, P.ldd, W, P.n, nk) < 0 ||
+                    hipStreamSynchronize(c->stream) != hipSuccess))  // W is the caller's
         st = set_error(c, CAL_ERR_HIP, "cal_prop_set_drive: upload failed");
     if (st < 0) {  // nothing was written to the matrix yet
         hipFree(P.d_v0);
@@ -746,7 +704,7 @@ int cal_prop_set_drive(cal_ctx* c, int nk, const double* W) {
 }
 
 int cal_prop_refresh_shifts(cal_ctx* c) {
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_refresh_shifts: no active propagator");
+    CAL_TRY(active_prop(c, "cal_prop_refresh_shifts", false));
     PropState& P = *c->prop;
     if (!P.newton) return 0;
     P.have_shifts = false;
@@ -755,7 +713,7 @@ int cal_prop_refresh_shifts(cal_ctx* c) {
 }
 
 int cal_prop_get(cal_ctx* c, double* psi_re, double* psi_im, cal_prop_info* info) {
-    if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, "cal_prop_get: no active propagator");
+    CAL_TRY(active_prop(c, "cal_prop_get", false));
     hipSetDevice(c->device);
     PropState& P = *c->prop;
     if (psi_re) CAL_HIP(c, hipMemcpyAsync(psi_re, P.psi(c), P.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));

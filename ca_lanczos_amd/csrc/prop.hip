@@ -22,7 +22,10 @@
 // order): launch_reduce turns them into the next step's squared norm without
 // another sweep, deterministically (no atomics).
 //
-// OBS = true (launch_prop_combine_obs) also reduces observables of the new
+// launch_prop_combine is the one host entry: it picks OBS and ABS from what
+// its PropCombine carries and VT / VB from the alignment of Q and out.
+//
+// OBS = true (nw + np > 0) also reduces observables of the new
 // state in the same sweep: nw real diagonal operators W_k and np reference
 // states phi_r = pr + i pi, each streamed once (a lane's two adjacent rows
 // with one 16-byte load: the library's own aligned allocation with an even
@@ -38,7 +41,7 @@
 // cap with wave-uniform guards, so every accumulator is a register.  The nrm
 // chain and the stores are those of OBS = false: same state, same norm bits.
 //
-// ABS = true (launch_prop_combine_masked) multiplies the new state by a real
+// ABS = true (a mask is given) multiplies the new state by a real
 // diagonal mask 0 <= M <= 1 before it is stored (the absorbing boundary: the
 // first-order splitting of a complex absorbing potential -ln(M)/dt) and sums
 // what the mask removes.  The mask is streamed once from the library's own
@@ -319,32 +322,24 @@ int prop_combine_blocks(int64_t n) {
     return (int)(b < 1 ? 1 : b);
 }
 
-template <bool OBS, bool ABS>
-static hipError_t launch_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                                 double* out, double* partial, PropObsArg<OBS, ABS> obs, hipStream_t st) {
-    if (n < 1 || m < 1 || m > kPropMaxCols || ld < 2 * n) return hipErrorInvalidValue;
-    if (n > ((int64_t)1 << 40)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)prop_combine_blocks(n)), block(kPropThreads);
-    // a half takes 16-byte accesses when its rows of every column and of the
-    // output start 16-byte aligned (even leading dimension)
-    const bool even = (ld & 1) == 0;
-    const bool vt = even && aligned16(Q) && aligned16(out);
-    const bool vb = even && aligned16(Q + n) && aligned16(out + n);
-    if (vt && vb)
-        hipLaunchKernelGGL((k_prop_combine<true, true, OBS, ABS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
-    else if (vt)
-        hipLaunchKernelGGL((k_prop_combine<true, false, OBS, ABS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
-    else if (vb)
-        hipLaunchKernelGGL((k_prop_combine<false, true, OBS, ABS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial, obs);
-    else
-        hipLaunchKernelGGL((k_prop_combine<false, false, OBS, ABS>), grid, block, 0, st, Q, ld, n, m, a, b, out, partial,
-                           obs);
-    return hipGetLastError();
-}
+int prop_combine_quantities(const PropCombine& p) { return 1 + p.obs.nw + 2 * p.obs.np + (p.mask ? 1 : 0); }
 
-hipError_t launch_prop_combine(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                               double* out, double* partial, hipStream_t st) {
-    return launch_combine<false, false>(Q, ld, n, m, a, b, out, partial, PropObsArg<false, false>{}, st);
+// the VT / VB choice: a half takes 16-byte accesses when its rows of every
+// column and of the output start 16-byte aligned (even leading dimension)
+template <bool OBS, bool ABS>
+static hipError_t launch_combine(const PropCombine& p, PropObsArg<OBS, ABS> obs, hipStream_t st) {
+    const dim3 grid((unsigned)prop_combine_blocks(p.n)), block(kPropThreads);
+    const bool even = (p.ld & 1) == 0;
+    const bool vt = even && aligned16(p.Q) && aligned16(p.out);
+    const bool vb = even && aligned16(p.Q + p.n) && aligned16(p.out + p.n);
+    auto launch = [&](auto k) {
+        hipLaunchKernelGGL(k, grid, block, 0, st, p.Q, p.ld, p.n, p.m, p.a, p.b, p.out, p.partial, obs);
+    };
+    if (vt && vb) launch(k_prop_combine<true, true, OBS, ABS>);
+    else if (vt) launch(k_prop_combine<true, false, OBS, ABS>);
+    else if (vb) launch(k_prop_combine<false, true, OBS, ABS>);
+    else launch(k_prop_combine<false, false, OBS, ABS>);
+    return hipGetLastError();
 }
 
 // the observables' counts, arrays and 16-byte loads
@@ -357,29 +352,17 @@ static bool obs_arg_ok(const PropObs& o, int64_t n) {
     return true;
 }
 
-hipError_t launch_prop_combine_obs(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                                   double* out, double* partial, const PropObs& o, hipStream_t st) {
-    if (!obs_arg_ok(o, n)) return hipErrorInvalidValue;
-    PropObsArg<true, false> arg;
-    arg.o = o;
-    return launch_combine<true, false>(Q, ld, n, m, a, b, out, partial, arg, st);
-}
-
-hipError_t launch_prop_combine_masked(const double* Q, int64_t ld, int64_t n, int m, const double* a, const double* b,
-                                      double* out, double* partial, const PropObs& o, const double* mask,
-                                      int64_t ldm, hipStream_t st) {
-    if (!obs_arg_ok(o, n)) return hipErrorInvalidValue;
+hipError_t launch_prop_combine(const PropCombine& p, hipStream_t st) {
+    if (p.n < 1 || p.m < 1 || p.m > kPropMaxCols || p.ld < 2 * p.n) return hipErrorInvalidValue;
+    if (p.n > ((int64_t)1 << 40)) return hipErrorInvalidValue;
+    if (!obs_arg_ok(p.obs, p.n)) return hipErrorInvalidValue;
     // the mask's 16-byte loads: the rules of the observables' columns
-    if (!mask || !aligned16(mask) || ldm < n || (ldm & 1) != 0) return hipErrorInvalidValue;
-    if (o.nw + o.np == 0) {
-        PropObsArg<false, true> arg;
-        arg.mask = mask;
-        return launch_combine<false, true>(Q, ld, n, m, a, b, out, partial, arg, st);
-    }
-    PropObsArg<true, true> arg;
-    arg.o = o;
-    arg.mask = mask;
-    return launch_combine<true, true>(Q, ld, n, m, a, b, out, partial, arg, st);
+    if (p.mask && (!aligned16(p.mask) || p.ldm < p.n || (p.ldm & 1) != 0)) return hipErrorInvalidValue;
+    const bool obs = p.obs.nw + p.obs.np > 0;
+    if (!obs && !p.mask) return launch_combine(p, PropObsArg<false, false>{}, st);
+    if (!p.mask) return launch_combine(p, PropObsArg<true, false>{p.obs}, st);
+    if (!obs) return launch_combine(p, PropObsArg<false, true>{p.mask}, st);
+    return launch_combine(p, PropObsArg<true, true>{p.obs, p.mask}, st);
 }
 
 // ---- the time-dependent diagonal ---------------------------------------------------

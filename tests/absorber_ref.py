@@ -18,23 +18,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import prop_obs_ref as pref  # noqa: E402
+from prop_obs_ref import combine_ref  # noqa: E402,F401  (the plain combine's chain)
 
 EPS = np.finfo(float).eps
-
-
-def combine_ref(Q, c):
-    """The plain combine's chain (tests/test_gpu_prop.py's, restated so that
-    CPU tests need not import a GPU test module)."""
-    n = Q.shape[0] // 2
-    a, b = c.real, c.imag
-    top, bot = np.zeros(n), np.zeros(n)
-    for j in range(Q.shape[1]):
-        qt, qb = Q[:n, j], Q[n:, j]
-        top = top + qt * a[j]
-        top = top - qb * b[j]
-        bot = bot + qt * b[j]
-        bot = bot + qb * a[j]
-    return top, bot
 
 
 def masked_ref(top, bot, M):

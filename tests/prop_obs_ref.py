@@ -23,6 +23,22 @@ import scipy.sparse as sp
 EPS = np.finfo(float).eps
 
 
+# ---- the combine sweep's chain -----------------------------------------------------
+def combine_ref(Q, c):
+    """(Re, Im) of Q_c c on stacked halves in the kernel's order: one chain
+    per output row, j ascending, no contraction (k_prop_combine)."""
+    n = Q.shape[0] // 2
+    a, b = c.real, c.imag
+    top, bot = np.zeros(n), np.zeros(n)
+    for j in range(Q.shape[1]):
+        qt, qb = Q[:n, j], Q[n:, j]
+        top = top + qt * a[j]
+        top = top - qb * b[j]
+        bot = bot + qt * b[j]
+        bot = bot + qb * a[j]
+    return top, bot
+
+
 # ---- the reference values and their bars -----------------------------------------
 def w_ref(W, psi):
     """(<W_k> for every column of W (n x nw), the rounding bars)."""

@@ -15,11 +15,16 @@ Bars:
     conserved to the same bar at every step.
 """
 import functools
+import os
+import sys
 
 import numpy as np
 import pytest
 import scipy.linalg as sl
 import scipy.sparse as sp
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from prop_obs_ref import combine_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(float).eps
@@ -76,20 +81,7 @@ def oracle_error(N, s, blocks, basis, dt, steps):
     return np.linalg.norm(x[:N] + 1j * x[N:] - exact(ew, U, psi0, steps * dt))
 
 
-# ---- 1. the combine kernel ---------------------------------------------------------
-def combine_ref(Q, c):
-    n = Q.shape[0] // 2
-    a, b = c.real, c.imag
-    top, bot = np.zeros(n), np.zeros(n)
-    for j in range(Q.shape[1]):
-        qt, qb = Q[:n, j], Q[n:, j]
-        top = top + qt * a[j]
-        top = top - qb * b[j]
-        bot = bot + qt * b[j]
-        bot = bot + qb * a[j]
-    return top, bot
-
-
+# ---- 1. the combine kernel (its NumPy chain: prop_obs_ref.combine_ref) ------------------
 @pytest.fixture(scope="module")
 def ctx(cal):
     c = cal.Context()

@@ -18,8 +18,8 @@ import scipy.sparse as sp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import prop_obs_ref as pref  # noqa: E402
+from prop_obs_ref import combine_ref  # noqa: E402
 from split_cases import lap3d_v, potential  # noqa: E402
-from test_gpu_prop import combine_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(float).eps
@@ -70,6 +70,21 @@ def test_combine_obs_caps(cal, ctx):
     out, n2, wv, ov = ctx.prop_combine_obs(Q, c, None, None)  # nothing set: the plain results
     plain, n2p = ctx.prop_combine(Q, c)
     assert np.array_equal(out, plain) and n2 == n2p and wv.size == 0 and ov.size == 0
+
+
+@pytest.mark.parametrize("m", [1, 24])
+@pytest.mark.parametrize("n", [1, 2, 3, 257, 1025])
+def test_combine_obs_without_observables_is_the_plain_kernel(ctx, n, m):
+    """No W and no phi: the sweep takes the kernel without observables, and
+    out and norm2 are the plain entry's to the bit (the odd last row, the
+    unaligned lower half, more than one block)."""
+    rng = np.random.RandomState(7000 * m + n)
+    Q = np.asfortranarray(rng.randn(2 * n, m))
+    c = rng.randn(m) + 1j * rng.randn(m)
+    out, n2, wv, ov = ctx.prop_combine_obs(Q, c)
+    plain, n2p = ctx.prop_combine(Q, c)
+    assert np.array_equal(out, plain) and n2 == n2p
+    assert wv.shape == (0,) and ov.shape == (0,)
 
 
 # ---- 2. - 4. the oscillator: one run with observables, one without -------------------------
@@ -155,6 +170,34 @@ def test_values_against_the_exact_solution(cal, N):
         assert dE <= pe + ebar
         ebars.append(pe + ebar)
     assert np.max(h["energy"]) - np.min(h["energy"]) <= 2 * max(ebars)
+
+
+@pytest.mark.parametrize("N", [256, 255])
+def test_energy_alone_does_not_disturb_the_run(cal, N):
+    """set_observables(energy=True) alone: the combine is the plain kernel's,
+    so the state has the bits of a run without observables, and every row
+    holds to the derived bars with no W and no phi."""
+    H, psi0, _, _, _ = pref.oscillator(N)
+    none = np.zeros((N, 0))
+    states = {}
+    for name in ("energy", "plain"):
+        P = cal.Propagator(H, psi0, S, BLOCKS, basis="newton")
+        try:
+            if name == "energy":
+                P.set_observables(energy=True)
+            states[name] = []
+            for _ in range(3):
+                assert P.step(DT, 1) == 0
+                states[name].append(P.state())
+            hist = P.observables()
+        finally:
+            P.close()
+        if name == "energy":
+            h = rows(hist)
+    assert h.shape == (3, 3)
+    for k in range(3):
+        assert np.array_equal(states["energy"][k], states["plain"][k])
+        pref.check_row(h[k], H, states["energy"][k], none, none, energy=True)
 
 
 # ---- 5. split-format Hamiltonian, complex state --------------------------------------------
