@@ -116,6 +116,7 @@ SIGNATURES = [
     ("cal_spmv_plane_info", c_int, [c_void_p, POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
     ("cal_spmv_format", c_int, [c_void_p, ip, ip, ip]),
     ("cal_spmv_split_info", c_int, [c_void_p, ip, POINTER(c_int64), ip, ip]),
+    ("cal_spmv_shared_info", c_int, [c_void_p, ip, POINTER(c_int64), POINTER(c_int64)]),
     ("cal_split_analyze", c_int, [c_int64, POINTER(c_int64), POINTER(c_int32), dp, POINTER(c_int64), ip, ip]),
     ("cal_bench_spmv", c_int, [c_void_p, c_int, c_double, dp, dp]),
     ("cal_spmv", c_int, [c_void_p, dp, dp]),

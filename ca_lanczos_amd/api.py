@@ -23,7 +23,12 @@ from .matrices import to_csr
 
 class Context:
     """A device context (``cal_ctx``): one HIP stream, the resident matrix and
-    the device-resident CA-Lanczos state."""
+    the device-resident CA-Lanczos state.
+
+    ``spmv_format`` (cal_set_spmv_format; default ``CAL_SPMV_FORMAT`` or
+    "auto") is "auto", "csr", "pattern", "split" or "shared".  "shared" is
+    opt-in and takes ``set_matrix_stacked`` only: blkdiag(H, H) with H stored
+    once (``spmv_shared_info``)."""
 
     def __init__(self, device: int | None = None, spmv_format: str | None = None, orth_coef: str | None = None,
                  mpk_depth: int | None = None, normalize: str | None = None):
@@ -149,6 +154,16 @@ class Context:
                                               ctypes.byref(ng)))
         return bool(on.value), P.value, H.value, bool(ng.value)
 
+    def spmv_shared_info(self):
+        """(on, n, nnz stored) of the shared stacked format
+        (``spmv_format="shared"`` with ``set_matrix_stacked``): blkdiag(H, H)
+        with the n x n H stored once; (False, 0, 0) for any other matrix.
+        ``spmv_format()`` reports "csr" and ``matrix_info()`` the logical 2n
+        rows and 2 nnz(H) for such a matrix."""
+        on, n, nz = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        check(self.h, lib.cal_spmv_shared_info(self.h, ctypes.byref(on), ctypes.byref(n), ctypes.byref(nz)))
+        return bool(on.value), n.value, nz.value
+
     def close(self):
         if self.h:
             lib.cal_destroy(self.h)
@@ -176,7 +191,10 @@ class Context:
 
     def set_matrix_stacked(self, H):
         """blkdiag(H, H) through cal_set_matrix_csr_stacked: the real form of
-        a complex problem on stacked vectors [Re; Im] (the time propagator)."""
+        a complex problem on stacked vectors [Re; Im] (the time propagator).
+        On a ``spmv_format="shared"`` context H is stored once and serves both
+        halves (same bits as the stacked "csr" context); that format takes no
+        other way of setting a matrix."""
         H = to_csr(H)
         if H.shape[0] != H.shape[1]:
             raise ValueError("H must be square")

@@ -233,11 +233,19 @@ struct DevMatrix {
     double* ds_diag = nullptr;       // n + 2 doubles
     double* ds_gsum = nullptr;       // PatArgs::gsum
     double* ds_dprod = nullptr;      // PatArgs::dprod
+    // The shared stacked format (cal_set_spmv_format "shared"):
+    // the matrix is blkdiag(H, H) of n_local = 2 n_half rows, but rowptr / col /
+    // val / blk / nblk / nit describe H alone (n_half rows, nnz entries; nnz_loc
+    // stays the logical 2 nnz).  Only the shared SpMV, the diagonal helpers and
+    // shared_refuses' callers may read the CSR arrays of such a matrix.
+    bool shared = false;
+    int64_t n_half = 0;
     // The stored diagonal's positions (runtime.cpp diag_positions; built at the
     // first cal_set_diagonal / cal_prop_set_drive, never at upload): val[dpos[r]]
     // is the entry of row r with col == r.  dpos_state: 0 not looked for, 1
     // every row has exactly one, -1 a row has none / more than one (the counts
     // in dpos_missing / dpos_dup; dpos is then not to be used)
+    // (a shared matrix: H's n_half positions, one slot for both halves)
     int* dpos = nullptr;
     int dpos_state = 0;
     int64_t dpos_missing = 0, dpos_dup = 0;
@@ -259,6 +267,10 @@ struct StdLanczosState;  // lanczos_std.cpp
 
 // Launchers (kernels.hip).  All enqueue on `st` and return hipError_t.
 hipError_t launch_spmv(const SpmvArgs& a, hipStream_t st);
+// the shared stacked SpMV (k_spmv_shared): a holds H's CSR arrays and row
+// blocks, the vectors have 2 n_half rows; modes 0, 1, 2 and 4 (mode 4 writes
+// 2 a.nblk partials: the top half's, then the bottom half's)
+hipError_t launch_spmv_shared(const SpmvArgs& a, int64_t n_half, hipStream_t st);
 hipError_t launch_spmv_pat(const PatArgs& a, hipStream_t st);
 // mode 4's grid = its number of y'x partials (0: this storage has no fused
 // Lanczos mode -- the row-pattern kernels k_spmv_pat / k_spmv_pat_lds)
@@ -638,7 +650,7 @@ struct cal_ctx {
     std::vector<CalTimerRec> timers;
     std::vector<hipEvent_t> event_pool;
 
-    int spmv_format = 0;  // 0 auto, 1 CSR, 2 row-pattern, 3 diagonal split (applies at the next set_matrix)
+    int spmv_format = 0;  // 0 auto, 1 CSR, 2 row-pattern, 3 diagonal split, 4 shared stacked (applies at the next set_matrix)
     int mpk_depth_req = 8;
     // schedule of the last powers_dev call (cal_mpk_schedule): 0 one halo
     // exchange per SpMV, 1 one deep exchange, 2 deep exchange on the RCCL
@@ -755,6 +767,18 @@ int ensure_pub(cal_ctx* c);
 int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, int64_t n_global, int64_t row0,
                   int64_t nghost, int64_t lpad, int64_t rext, const std::vector<int>& rowptr,
                   const std::vector<int>& col, const double* val);
+// The "shared" format's upload (cal_set_matrix_csr_stacked): H alone, n rows,
+// as the matrix blkdiag(H, H) of 2n rows (DevMatrix::shared).
+int upload_matrix_shared(cal_ctx* c, int64_t n, const std::vector<int>& rowptr, const std::vector<int>& col,
+                         const double* val);
+// The one place that decides what a shared matrix refuses: 0 for any other
+// matrix; on a shared one CAL_ERR_UNSUPPORTED, with a message that names `what`
+// and the "csr" format.  Every reader of A.rowptr / col / val / blk / nblk other
+// than the shared SpMV and the diagonal helpers asks it first, so nothing
+// indexes rowptr past H's n_half rows.
+int shared_refuses(cal_ctx* c, const char* what);
+// "shared" selected on the context: only cal_set_matrix_csr_stacked sets a matrix
+int shared_format_only_stacked(cal_ctx* c, const char* who);
 // Row-pattern SpMV over stored rows [o, o+len) (o even); x, y at the local origin.
 int spmv_range(cal_ctx* c, int64_t o, int64_t len, const double* x, double* y, int mode, double shift, double im2,
                const double* xprev);

@@ -346,6 +346,7 @@ int cal_set_matrix_csr_dist(cal_ctx* c, int64_t n_global, int64_t row0, int64_t 
                             const int64_t* colind_global, const double* val) {
     if (!c || nlocal < 0 || row0 < 0 || row0 + nlocal > n_global || !rowptr)
         return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csr_dist: bad arguments");
+    CAL_TRY(shared_format_only_stacked(c, "cal_set_matrix_csr_dist"));
     hipSetDevice(c->device);
     const int nranks = c->comm ? c->comm->nranks : 1;
     const int rank = c->comm ? c->comm->rank : 0;

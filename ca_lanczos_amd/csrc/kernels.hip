@@ -12,6 +12,8 @@
 //                   MODE 4 (here, in k_spmv_pair and in k_spmv_planes): the
 //                   standard Lanczos step y = A x - beta xprev with the block
 //                   partials of y'x (lanczos.m:103-107; lz_sub, lz_block_sum).
+//   k_spmv_shared   the same on blkdiag(H, H) with H stored once: one load of
+//                   col / val, two gathers, two products, both halves' rows.
 //   k_spmv_pat_lds, k_spmv_pair
 //                   row-pattern SpMV (lossless pattern table, one / two rows
 //                   per lane), same arithmetic, same shift epilogue; the pair
@@ -270,6 +272,184 @@ hipError_t launch_spmv(const SpmvArgs& a0, hipStream_t st) {
         case 2: return launch_spmv_mode<2>(a, nit, st);
         case 3: return a.xnrm ? launch_spmv_mode<3>(a, nit, st) : hipErrorInvalidValue;
         case 4: return a.dotp ? launch_spmv_mode<4>(a, nit, st) : hipErrorInvalidValue;
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// --------------------------------------------------------------------------
+// The shared stacked SpMV ("shared"): y = blkdiag(H, H) x on the
+// stacked vectors [Re; Im] of 2 nh rows with H stored once.  The grid, the row
+// blocks and the load phase are k_spmv's over H's nh rows; every nonzero is
+// loaded once, gathers x[c] and x[nh + c], and its two products go to LDS.
+// Thread <-> row as in k_spmv, so each half's row sums -- and MODE 4's block
+// partials, dotp[b] for the top half and dotp[nblk + b] for the bottom one --
+// are the bits k_spmv gives on the stacked matrix (whose row blocks then do
+// not straddle row nh).  MODE 3 (normest) is not built.
+//
+// The two products of a nonzero are one 16-B LDS element (one ds_write_b128,
+// one ds_read_b128 per j of the row sum); CAL_SHARED_LDS_SPLIT = 1 keeps them
+// in two 8-B arrays instead (the A/B of DESIGN.md §3; 32 KiB either way).
+#ifndef CAL_SHARED_LDS_SPLIT
+#define CAL_SHARED_LDS_SPLIT 0
+#endif
+struct SharedProd {
+#if CAL_SHARED_LDS_SPLIT
+    double p0[kSpmvNnz], p1[kSpmvNnz];
+    __device__ __forceinline__ void put(int q, double a, double b) {
+        p0[q] = a;
+        p1[q] = b;
+    }
+    __device__ __forceinline__ void add(int q, double& s0, double& s1) const {
+        s0 = s0 + p0[q];
+        s1 = s1 + p1[q];
+    }
+#else
+    d2 p[kSpmvNnz];
+    __device__ __forceinline__ void put(int q, double a, double b) {
+        d2 t;
+        t.x = a;
+        t.y = b;
+        p[q] = t;
+    }
+    __device__ __forceinline__ void add(int q, double& s0, double& s1) const {
+        const d2 t = p[q];
+        s0 = s0 + t.x;
+        s1 = s1 + t.y;
+    }
+#endif
+};
+
+template <int MODE, int NIT, bool NT>
+__global__ __launch_bounds__(kSpmvThreads) void k_spmv_shared(SpmvArgs a, int nh) {
+    static_assert(MODE == 0 || MODE == 1 || MODE == 2 || MODE == 4, "k_spmv_shared: modes 0, 1, 2 and 4");
+    __shared__ SharedProd prod;
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tid = threadIdx.x;
+    const int r0 = a.blk[b], r1 = a.blk[b + 1];
+    const int p0 = a.rowptr[r0], p1 = a.rowptr[r1];
+    const int cnt = p1 - p0;
+    const double* xb = a.x + nh;  // the bottom half
+    const bool lzhas = MODE == 4 && a.xprev && a.pb2;
+    const double lzb = lzhas ? sqrt(*a.pb2) : 0.0;
+    const double* lzq = lzhas ? a.xprev : a.x;
+    double lzd0 = 0.0, lzd1 = 0.0;  // MODE 4: the thread's y * x, per half
+    if (cnt <= kSpmvNnz) {
+        if (cnt > 0) {
+            // k_spmv's phases: all col / val loads (clamped, unbranched), then
+            // both gathers of every nonzero, then the LDS products
+            const int pl = p1 - 1;
+            int ci[NIT];
+            double v[NIT], x0[NIT], x1[NIT];
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int p = min(p0 + it * kSpmvThreads + tid, pl);
+                ci[it] = ldnt<NT>(a.col + p);
+                v[it] = ldnt<NT>(a.val + p);
+            }
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                x0[it] = a.x[ci[it]];
+                x1[it] = xb[ci[it]];
+            }
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int q = it * kSpmvThreads + tid;
+                if (q < cnt) prod.put(q, v[it] * x0[it], v[it] * x1[it]);
+            }
+        }
+        __syncthreads();
+        const int r = r0 + tid;
+        if (r < r1) {
+            const int q0 = a.rowptr[r] - p0, q1 = a.rowptr[r + 1] - p0;
+            double s0 = 0.0, s1 = 0.0;
+            for (int j = q0; j < q1; ++j) prod.add(j, s0, s1);
+            if (MODE == 4) {
+                const double y0 = lz_sub(s0, lzb, lzq[r], lzhas);
+                const double y1 = lz_sub(s1, lzb, lzq[nh + r], lzhas);
+                a.y[r] = y0;
+                a.y[nh + r] = y1;
+                lzd0 = y0 * a.x[r];
+                lzd1 = y1 * xb[r];
+            } else {
+                a.y[r] = spmv_epilogue<MODE>(s0, a, r);
+                a.y[nh + r] = spmv_epilogue<MODE>(s1, a, nh + r);
+            }
+        }
+    } else {
+        // one long row (> kSpmvNnz nonzeros): chunked, both sums still in order
+        double s0 = 0.0, s1 = 0.0;
+        for (int c = p0; c < p1; c += kSpmvNnz) {
+            const int m = min(kSpmvNnz, p1 - c);
+            for (int q = tid; q < m; q += kSpmvThreads) {
+                const int cc = a.col[c + q];
+                const double vq = a.val[c + q];
+                prod.put(q, vq * a.x[cc], vq * xb[cc]);
+            }
+            __syncthreads();
+            if (tid == 0)
+                for (int j = 0; j < m; ++j) prod.add(j, s0, s1);
+            __syncthreads();
+        }
+        if (tid == 0) {  // the one thread that holds the row's sums
+            if (MODE == 4) {
+                const double y0 = lz_sub(s0, lzb, lzq[r0], lzhas);
+                const double y1 = lz_sub(s1, lzb, lzq[nh + r0], lzhas);
+                a.y[r0] = y0;
+                a.y[nh + r0] = y1;
+                lzd0 = y0 * a.x[r0];
+                lzd1 = y1 * xb[r0];
+            } else {
+                a.y[r0] = spmv_epilogue<MODE>(s0, a, r0);
+                a.y[nh + r0] = spmv_epilogue<MODE>(s1, a, nh + r0);
+            }
+        }
+    }
+    if constexpr (MODE == 4) {
+        // the wave sums reuse the products' LDS once every row is summed: 32 KiB
+        // is five blocks per CU, 64 bytes more would be four
+        __syncthreads();
+        double* ws = reinterpret_cast<double*>(&prod);
+        const double t0 = lz_block_sum<kSpmvThreads / 64>(lzd0, ws);
+        const double t1 = lz_block_sum<kSpmvThreads / 64>(lzd1, ws + kSpmvThreads / 64);
+        if (tid == 0) {
+            a.dotp[b] = t0;
+            a.dotp[gridDim.x + b] = t1;
+        }
+    }
+}
+
+template <int MODE, bool NT>
+static hipError_t launch_spmv_shared_nit(const SpmvArgs& a, int nh, int nit, hipStream_t st) {
+    dim3 g(a.nblk), b(kSpmvThreads);
+    switch (nit) {
+        case 1: hipLaunchKernelGGL((k_spmv_shared<MODE, 1, NT>), g, b, 0, st, a, nh); break;
+        case 2: hipLaunchKernelGGL((k_spmv_shared<MODE, 2, NT>), g, b, 0, st, a, nh); break;
+        case 3: hipLaunchKernelGGL((k_spmv_shared<MODE, 3, NT>), g, b, 0, st, a, nh); break;
+        case 4: hipLaunchKernelGGL((k_spmv_shared<MODE, 4, NT>), g, b, 0, st, a, nh); break;
+        case 5: hipLaunchKernelGGL((k_spmv_shared<MODE, 5, NT>), g, b, 0, st, a, nh); break;
+        case 6: hipLaunchKernelGGL((k_spmv_shared<MODE, 6, NT>), g, b, 0, st, a, nh); break;
+        case 7: hipLaunchKernelGGL((k_spmv_shared<MODE, 7, NT>), g, b, 0, st, a, nh); break;
+        default: hipLaunchKernelGGL((k_spmv_shared<MODE, 8, NT>), g, b, 0, st, a, nh); break;
+    }
+    return hipGetLastError();
+}
+
+template <int MODE>
+static hipError_t launch_spmv_shared_mode(const SpmvArgs& a, int nh, int nit, hipStream_t st) {
+    return a.nt ? launch_spmv_shared_nit<MODE, true>(a, nh, nit, st) : launch_spmv_shared_nit<MODE, false>(a, nh, nit, st);
+}
+
+// a: H's CSR arrays and row blocks (a.nblk of them), x / y / xprev the stacked
+// vectors of 2 n_half rows, mode | nit << 8 as for launch_spmv
+hipError_t launch_spmv_shared(const SpmvArgs& a, int64_t n_half, hipStream_t st) {
+    if (a.nblk <= 0) return hipSuccess;
+    if (n_half < 1 || 2 * n_half >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const int nit = (a.mode >> 8) & 0xff, nh = (int)n_half;
+    switch (a.mode & 0xff) {
+        case 0: return launch_spmv_shared_mode<0>(a, nh, nit, st);
+        case 1: return launch_spmv_shared_mode<1>(a, nh, nit, st);
+        case 2: return a.xprev ? launch_spmv_shared_mode<2>(a, nh, nit, st) : hipErrorInvalidValue;
+        case 4: return a.dotp ? launch_spmv_shared_mode<4>(a, nh, nit, st) : hipErrorInvalidValue;
         default: return hipErrorInvalidValue;
     }
 }

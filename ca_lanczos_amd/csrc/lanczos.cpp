@@ -159,6 +159,7 @@ static int enqueue_powers(cal_ctx* c, LanczosState& L, int k) {
 static int normest_dev(cal_ctx* c, double* out) {
     constexpr int kNormestChunk = 8;
     constexpr size_t kNrm = 4096;  // d_red / h_red offset (orth_device uses [0, 4096))
+    CAL_TRY(shared_refuses(c, "normest"));
     const int64_t n = c->A.n_local, ld = c->A.ld;
     CAL_TRY(ensure_work(c, 2, ld));
     CAL_TRY(ensure_red(c, kNrm + 2 * kNormestChunk));
@@ -333,6 +334,7 @@ static int normest_async_enqueue_chunk(cal_ctx* c, NormestAsync& J) {
 }
 
 static int normest_async_begin(cal_ctx* c, NormestAsync& J) {
+    CAL_TRY(shared_refuses(c, "normest"));
     J = NormestAsync();
     const int64_t n = c->A.n_local;
     const int nb = dot_blocks(n);
@@ -713,6 +715,7 @@ static int diag_reserve(cal_ctx* c, LanczosState& L) {
 }
 
 static int diag_launch(cal_ctx* c, LanczosState& L, DiagJob& J) {
+    CAL_TRY(shared_refuses(c, "the Ritz residual"));
     const int s = L.s, sk = s * J.k;
     const int64_t n = c->A.n_local, ld = c->A.ld;
     const hipStream_t main = c->stream, aux = c->stream;
@@ -1422,6 +1425,8 @@ int lanczos_begin(cal_ctx* c, const LanczosBegin& in, int s, int max_outer, cons
         return set_error(c, CAL_ERR_ARG, "ca_lanczos.m: Invalid option value for orth: " + o);
     if (b != "monomial" && b != "newton") return set_error(c, CAL_ERR_ARG, "ERROR: Unknown basis type: " + b);
     if (in.shifts && in.nshifts < s) return set_error(c, CAL_ERR_ARG, "lanczos_begin: fewer than s Newton shifts");
+    // normest: refused before the previous run's state is touched
+    if (o == "periodic" || o == "selective") CAL_TRY(shared_refuses(c, ("orth = '" + o + "' (normest)").c_str()));
     hipSetDevice(c->device);
     // the previous run's Q / V buffers, kept when the shapes match
     double *keepQ = nullptr, *keepV = nullptr;
@@ -1513,6 +1518,7 @@ int cal_lanczos_begin(cal_ctx* c, const double* r, int s, int max_outer, const c
 
 int cal_lanczos_step(cal_ctx* c, int diagnostics) {
     if (!c || !c->lz) return set_error(c, CAL_ERR_ARG, "cal_lanczos_step: no active CA-Lanczos run");
+    if (diagnostics) CAL_TRY(shared_refuses(c, "the Ritz diagnostics' residual"));
     hipSetDevice(c->device);
     return lanczos_step(c, diagnostics);
 }
@@ -1579,6 +1585,7 @@ int cal_lanczos_end(cal_ctx* c) {
 int cal_compute_ritz_rnorm(cal_ctx* c, const double* Q, int k, const double* Vp, const double* d, double* rn) {
     if (!c || !Q || !Vp || !d || !rn || k < 1) return CAL_ERR_ARG;
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    CAL_TRY(shared_refuses(c, "compute_ritz_rnorm"));
     const int64_t n = c->A.n_local, ld = c->A.ld;
     CAL_TRY(ensure_work(c, 2 * k, ld));
     double* Qd = work_col(c, 0) + c->A.lpad;
@@ -1592,6 +1599,7 @@ int cal_compute_ritz_rnorm(cal_ctx* c, const double* Q, int k, const double* Vp,
 // the same for Q already on the device (k columns at Qd, leading dimension
 // A.ld, local origin; not work columns [k, 2k), which hold X)
 int cal::ritz_rnorm_dev(cal_ctx* c, const double* Qd, int k, const double* Vp, const double* d, double* rn) {
+    CAL_TRY(shared_refuses(c, "compute_ritz_rnorm"));
     for (int i = 0; i < k; ++i)
         if (!std::isfinite(d[i])) return set_error(c, CAL_ERR_ARG, "compute_ritz_rnorm: non-finite eigenvalue");
     const int64_t n = c->A.n_local, ld = c->A.ld;
@@ -1669,6 +1677,7 @@ int cal_ca_lanczos(cal_ctx* c, const double* r, int s, int iter, const char* bas
     if (!c) return CAL_ERR_ARG;
     if (s < 1 || iter < 1) return set_error(c, CAL_ERR_ARG, "cal_ca_lanczos: need s >= 1 and iter >= 1");
     const int t = (iter + s - 1) / s;  // ca_lanczos.m:52
+    if (diagnostics) CAL_TRY(shared_refuses(c, "the Ritz diagnostics' residual"));  // before a run is opened
     CAL_TRY(cal_lanczos_begin(c, r, s, t, basis, orth));
     int status = 0;
     for (int k = 0; k < t; ++k) {
@@ -1689,6 +1698,7 @@ int cal_ca_lanczos(cal_ctx* c, const double* r, int s, int iter, const char* bas
 namespace {
 // ||A x - l x|| / ||l x|| of one device vector (ld layout, lpad origin)
 int rel_residual(cal_ctx* c, double* x, double l, double* out) {
+    CAL_TRY(shared_refuses(c, "the Ritz residual"));
     const int64_t n = c->A.n_local;
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + 255) / 256));
     CAL_TRY(ensure_partial(c, (size_t)2 * std::max(nb, spmv_resid_pair_blocks(c))));
@@ -1725,6 +1735,7 @@ int cal_restarted_ca_lanczos(cal_ctx* c, const double* r, int max_lanczos, int n
     if (!c || !r || n_wanted < 1 || s < 1 || s > kMaxS || !basis || !orth || !conv_eigs)
         return set_error(c, CAL_ERR_ARG, "restarted_ca_lanczos: bad arguments");
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    CAL_TRY(shared_refuses(c, "the restart drivers' normest and Ritz residuals"));
     std::string o(orth), b(basis);
     for (auto& ch : o) ch = (char)std::tolower(ch);
     for (auto& ch : b) ch = (char)std::tolower(ch);
@@ -2055,6 +2066,7 @@ int cal_impl_restarted_ca_lanczos(cal_ctx* c, const double* r, int max_lanczos, 
     if (!r || n_wanted < 1 || s < 1 || s > kMaxS || !basis || !orth || !conv_eigs)
         return set_error(c, CAL_ERR_ARG, "impl_restarted_ca_lanczos: bad arguments");
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    CAL_TRY(shared_refuses(c, "the restart drivers' normest and Ritz residuals"));
     std::string o(orth), b(basis);
     for (auto& ch : o) ch = (char)std::tolower(ch);
     for (auto& ch : b) ch = (char)std::tolower(ch);

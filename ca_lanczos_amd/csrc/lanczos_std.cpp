@@ -387,6 +387,7 @@ static int std_begin(cal_ctx* c, const double* r, int maxiter, const char* orth,
     const int64_t n = c->A.n_local, ld = c->A.ld;
     if (!r || maxiter < 1 || maxiter > n) return set_error(c, CAL_ERR_ARG, "lanczos: need r and 1 <= maxiter <= n");
     if (!keep_Q && mode != 0) return set_error(c, CAL_ERR_ARG, "lanczos: keep_Q = 0 needs orth = 'local'");
+    if (mode >= 2) CAL_TRY(shared_refuses(c, "orth = 'periodic' / 'selective' (normest)"));
     std_free(c);
     StdLanczosState* L = new StdLanczosState();
     c->slz = L;
@@ -452,6 +453,7 @@ int cal_std_lanczos_step(cal_ctx* c, int nsteps, int diagnostics) {
         return set_error(c, CAL_ERR_ARG, "cal_std_lanczos_step: nsteps runs past maxiter");
     if (diagnostics && !L.keep_Q)
         return set_error(c, CAL_ERR_ARG, "cal_std_lanczos_step: diagnostics need keep_Q");
+    if (diagnostics) CAL_TRY(shared_refuses(c, "the Ritz diagnostics' residual"));
     if (diagnostics && L.rn.empty()) L.rn.assign((size_t)L.m * L.m, 0.0);
     const bool host = diagnostics || L.mode >= 2;  // alpha, beta on the host every step
     const double t0 = now_ms();

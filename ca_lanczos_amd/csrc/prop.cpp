@@ -400,6 +400,26 @@ int cal_set_matrix_csr_stacked(cal_ctx* c, int64_t n, const int64_t* rowptr, con
     if (!c || n < 0 || !rowptr || (n > 0 && rowptr[n] > 0 && (!colind || !val)))
         return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csr_stacked: bad arguments");
     const int64_t nnz = rowptr[n];
+    if (c->spmv_format == 4) {
+        // the "shared" format: H alone goes up, nothing doubled on the host
+        if (c->comm && c->comm->nranks > 1)
+            return set_error(c, CAL_ERR_UNSUPPORTED, "cal_set_matrix_csr_stacked: the \"shared\" format runs on one "
+                                                     "rank (the context has a communicator of several ranks)");
+        if (nnz < 0 || nnz >= ((int64_t)1 << 31) || 2 * n >= ((int64_t)1 << 31))
+            return set_error(c, CAL_ERR_UNSUPPORTED, "cal_set_matrix_csr_stacked: 2n and nnz(H) must be < 2^31");
+        if (n < 1) return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csr_stacked: the \"shared\" format needs n >= 1");
+        hipSetDevice(c->device);
+        std::vector<int> rp(n + 1), col(nnz);
+        for (int64_t i = 0; i <= n; ++i) rp[i] = (int)rowptr[i];
+        for (int64_t i = 0; i < n; ++i)
+            if (rp[i + 1] < rp[i]) return set_error(c, CAL_ERR_ARG, "row pointers must be non-decreasing");
+        if (rp[0] != 0) return set_error(c, CAL_ERR_ARG, "row pointers must start at 0");
+        for (int64_t p = 0; p < nnz; ++p) {
+            if (colind[p] < 0 || colind[p] >= n) return set_error(c, CAL_ERR_ARG, "column index out of range");
+            col[p] = colind[p];
+        }
+        return upload_matrix_shared(c, n, rp, col, val);
+    }
     if (nnz < 0 || 2 * nnz >= ((int64_t)1 << 31) || 2 * n >= ((int64_t)1 << 31))
         return set_error(c, CAL_ERR_UNSUPPORTED, "n and nnz must be < 2^31 per rank");
     for (int64_t i = 0; i < n; ++i)

@@ -749,6 +749,83 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
     return 0;
 }
 
+// The shared stacked format: blkdiag(H, H) with H's CSR arrays stored once.
+// The vectors' layout (n_local = n_global = n_rows = 2n, lpad 0, ld) is what the
+// stacked CSR upload gives, so everything above the SpMV sees the same 2n-row
+// problem; the row blocks and nit are H's.  Never another storage.
+int upload_matrix_shared(cal_ctx* c, int64_t n, const std::vector<int>& rowptr, const std::vector<int>& col,
+                         const double* val) {
+    free_matrix(c);
+    DevMatrix& A = c->A;
+    A.shared = true;
+    A.n_half = n;
+    A.n_local = A.n_global = A.n_rows = 2 * n;
+    A.nnz = rowptr[n];         // stored
+    A.nnz_loc = 2 * A.nnz;     // of the matrix the context represents
+    A.lpad = 0;
+    A.ld = ((2 * n + 2 + 63) / 64) * 64;  // upload_matrix's, for 2n rows
+    if (A.ld == 0) A.ld = 64;
+    std::vector<int> blk;
+    int max_nnz = 0;
+    build_row_blocks(n, rowptr, blk, &max_nnz);
+    A.nblk = (int)blk.size() - 1;
+    A.nit = std::min(8, std::max(1, (max_nnz + 255) / 256));
+    CAL_HIP(c, hipMalloc((void**)&A.rowptr, (n + 1) * sizeof(int)));
+    CAL_HIP(c, hipMalloc((void**)&A.col, std::max<int64_t>(A.nnz, 1) * sizeof(int)));
+    CAL_HIP(c, hipMalloc((void**)&A.val, std::max<int64_t>(A.nnz, 1) * sizeof(double)));
+    CAL_HIP(c, hipMalloc((void**)&A.blk, blk.size() * sizeof(int)));
+    CAL_HIP(c, hipMemcpy(A.rowptr, rowptr.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice));
+    if (A.nnz > 0) {
+        CAL_HIP(c, hipMemcpy(A.col, col.data(), A.nnz * sizeof(int), hipMemcpyHostToDevice));
+        CAL_HIP(c, hipMemcpy(A.val, val, A.nnz * sizeof(double), hipMemcpyHostToDevice));
+    }
+    CAL_HIP(c, hipMemcpy(A.blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
+    c->has_A = true;
+    c->A_gen++;
+    return 0;
+}
+
+int shared_refuses(cal_ctx* c, const char* what) {
+    if (!c->has_A || !c->A.shared) return 0;
+    return set_error(c, CAL_ERR_UNSUPPORTED,
+                     std::string(what) + " reads the stored rows of the whole matrix, and the \"shared\" format stores "
+                                         "H of blkdiag(H, H) once: select the \"csr\" format (cal_set_spmv_format) "
+                                         "before cal_set_matrix_csr_stacked to get it");
+}
+
+int shared_format_only_stacked(cal_ctx* c, const char* who) {
+    if (c->spmv_format != 4) return 0;
+    return set_error(c, CAL_ERR_UNSUPPORTED,
+                     std::string(who) + ": the \"shared\" format stores H of blkdiag(H, H) once on one rank; its only "
+                                        "way of setting a matrix is cal_set_matrix_csr_stacked");
+}
+
+// the launch description of the shared stacked SpMV (H's arrays, 2 n_half-row vectors)
+static SpmvArgs shared_args(const DevMatrix& A, const double* x, double* y, int mode) {
+    SpmvArgs a;
+    a.rowptr = A.rowptr;
+    a.col = A.col;
+    a.val = A.val;
+    a.blk = A.blk;
+    a.nblk = A.nblk;
+    a.x = x;
+    a.y = y;
+    a.xprev = nullptr;
+    a.shift = 0.0;
+    a.im2 = 0.0;
+    a.xcd = 1;
+    a.mode = mode | (A.nit << 8);
+    // col + val of H against the 256 MB Infinity Cache
+    a.nt = (int64_t)12 * A.nnz > ((int64_t)256 << 20) ? 1 : 0;
+    return a;
+}
+
+// algorithmic bytes of a shared SpMV: H's col / val / rowptr once, x and y of
+// both halves, and the previous power / Lanczos vector when there is one
+static double shared_spmv_bytes(const DevMatrix& A, bool prev) {
+    return 12.0 * A.nnz + 4.0 * (A.n_half + 1) + 32.0 * A.n_half + (prev ? 16.0 * A.n_half : 0.0);
+}
+
 // ---- the stored diagonal as a device vector ---------------------------------
 // (cal_set_diagonal / cal_get_diagonal and the propagator's drive, prop.cpp)
 static int diag_supported(cal_ctx* c, const char* who) {
@@ -786,12 +863,13 @@ int diag_positions(cal_ctx* c) {
     CAL_TRY(diag_supported(c, "the diagonal"));
     DevMatrix& A = c->A;
     if (A.dpos_state != 0) return diag_verdict(c);
-    const int nb = diag_find_blocks(A.n_local);
+    const int64_t nr = A.shared ? A.n_half : A.n_local;  // the stored rows (a shared matrix: H's)
+    const int nb = diag_find_blocks(nr);
     CAL_TRY(ensure_partial(c, 2 * (size_t)nb));
     CAL_TRY(ensure_red(c, 2));
-    if (!A.dpos) CAL_HIP(c, hipMalloc((void**)&A.dpos, A.n_local * sizeof(int)));
-    const int t = timer_begin(c, 3, (double)A.n_local * 12.0 + (double)A.nnz * 4.0);
-    const hipError_t e = launch_diag_find(A.rowptr, A.col, A.n_local, A.dpos, c->d_partial, c->stream);
+    if (!A.dpos) CAL_HIP(c, hipMalloc((void**)&A.dpos, nr * sizeof(int)));
+    const int t = timer_begin(c, 3, (double)nr * 12.0 + (double)A.nnz * 4.0);
+    const hipError_t e = launch_diag_find(A.rowptr, A.col, nr, A.dpos, c->d_partial, c->stream);
     timer_end(c, t);
     if (e != hipSuccess) return hip_fail(c, e, "launch_diag_find");
     CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 2, c->d_red, c->stream));
@@ -811,6 +889,10 @@ int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int
     if (halves < 1 || halves > 2 || n < 1 || n * halves != A.n_local || nk < 0 || nk > kDriveMaxOps || !V0_dev ||
         (nk > 0 && (!W_dev || !f || ldw < n)))
         return set_error(c, CAL_ERR_ARG, "diag_update_dev: bad arguments");
+    if (A.shared) {  // both halves read one slot: it is written once, on H's rows
+        if (halves != 2) return set_error(c, CAL_ERR_ARG, "diag_update_dev: a shared matrix takes both halves at once");
+        halves = 1;
+    }
     DiagDrive a;
     a.V0 = V0_dev;
     a.W = W_dev;
@@ -834,6 +916,12 @@ int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int
 int diag_gather_dev(cal_ctx* c, double* dst, int64_t cnt) {
     CAL_TRY(diag_positions(c));
     if (!dst || cnt < 0 || cnt > c->A.n_local) return set_error(c, CAL_ERR_ARG, "diag_gather_dev: bad arguments");
+    if (c->A.shared) {  // dpos covers H's rows: the bottom half's entries are the same slots
+        const int64_t nh = c->A.n_half, top = std::min(cnt, nh);
+        CAL_HIP_OTHER(c, launch_gather(dst, c->A.val, c->A.dpos, top, c->stream));
+        if (cnt > nh) CAL_HIP_OTHER(c, launch_gather(dst + nh, c->A.val, c->A.dpos, cnt - nh, c->stream));
+        return 0;
+    }
     CAL_HIP_OTHER(c, launch_gather(dst, c->A.val, c->A.dpos, cnt, c->stream));
     return 0;
 }
@@ -954,6 +1042,7 @@ int spmv_range(cal_ctx* c, int64_t o, int64_t len, const double* x, double* y, i
 hipError_t spmv_on_stream(const cal_ctx* c, const double* x, double* y, int mode, const double* xnrm, hipStream_t st) {
     const DevMatrix& A = c->A;
     if (mode != 0 && mode != 3) return hipErrorInvalidValue;
+    if (A.shared) return hipErrorInvalidValue;  // normest's stream: refused before it starts (shared_refuses)
     if (A.use_pat) {
         if (mode != 0) return hipErrorInvalidValue;
         return launch_spmv_pat(pat_args(A, A.ext_off, A.n_local, x, y, 0, 0.0, 0.0, nullptr), st);
@@ -1037,6 +1126,19 @@ int spmv_dev(cal_ctx* c, const double* x, double* y, int mode, double shift, dou
              const double* xnrm) {
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
     if (mode == 3 && (c->A.use_pat || !xnrm)) return set_error(c, CAL_ERR_ARG, "spmv_dev: mode 3 needs CSR and xnrm");
+    if (c->A.shared) {
+        if (mode == 3) return shared_refuses(c, "normest");
+        if (mode < 0 || mode > 2 || (mode == 2 && !xprev)) return set_error(c, CAL_ERR_ARG, "spmv_dev: bad mode");
+        SpmvArgs a = shared_args(c->A, x, y, mode);
+        a.xprev = mode == 2 ? xprev : nullptr;
+        a.shift = shift;
+        a.im2 = im2;
+        c->stat_spmv_rows += c->A.n_local;
+        const int t = timer_begin(c, 0, shared_spmv_bytes(c->A, mode == 2));
+        CAL_HIP(c, launch_spmv_shared(a, c->A.n_half, c->stream));
+        timer_end(c, t);
+        return 0;
+    }
     CAL_TRY(halo_exchange(c, const_cast<double*>(x)));
     if (c->A.use_pat) return spmv_range(c, c->A.ext_off, c->A.n_local, x, y, mode, shift, im2, xprev);
     if (c->A.use_dsplit && mode != 3) {
@@ -1094,6 +1196,7 @@ static SpmvArgs csr_args(const cal_ctx* c, const double* x, double* y, int mode)
 int spmv_lanczos_parts(const cal_ctx* c, const double* x, const double* xprev, double* y) {
     const DevMatrix& A = c->A;
     if (!c->has_A || (c->comm && c->comm->nranks > 1)) return 0;
+    if (A.shared) return 2 * A.nblk;  // the top half's block partials, then the bottom half's
     if (A.use_dsplit) return spmv_dsplit_blocks(dsplit_args(A, x, y, 4, 0.0, 0.0, xprev));
     if (!A.use_pat) return spmv_lanczos_blocks(csr_args(c, x, y, 4));
     return spmv_pat_lanczos_blocks(pat_args(A, A.ext_off, A.n_local, x, y, 4, 0.0, 0.0, xprev));
@@ -1106,6 +1209,16 @@ int spmv_lanczos_dev(cal_ctx* c, const double* x, const double* xprev, const dou
         return set_error(c, CAL_ERR_ARG, "spmv_lanczos_dev: no fused Lanczos mode for this matrix");
     const bool has = xprev && pb2;
     c->stat_spmv_rows += A.n_local;
+    if (A.shared) {
+        SpmvArgs a = shared_args(A, x, y, 4);
+        a.xprev = has ? xprev : nullptr;
+        a.pb2 = has ? pb2 : nullptr;
+        a.dotp = dotp;
+        const int t = timer_begin(c, 0, shared_spmv_bytes(A, has));
+        CAL_HIP(c, launch_spmv_shared(a, A.n_half, c->stream));
+        timer_end(c, t);
+        return 0;
+    }
     if (A.use_pat) {
         PatArgs p = pat_args(A, A.ext_off, A.n_local, x, y, 4, 0.0, 0.0, has ? xprev : nullptr);
         p.pb2 = has ? pb2 : nullptr;
@@ -1418,6 +1531,7 @@ int cal_timer_read(cal_ctx* c, const char* kind, int64_t* count, double* total_m
 int cal_set_matrix_csr(cal_ctx* c, int64_t n, const int64_t* rowptr, const int32_t* colind, const double* val) {
     if (!c || n < 0 || !rowptr || (n > 0 && rowptr[n] > 0 && (!colind || !val)))
         return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csr: bad arguments");
+    CAL_TRY(shared_format_only_stacked(c, "cal_set_matrix_csr"));
     if (c->comm && c->comm->nranks > 1)
         return set_error(c, CAL_ERR_ARG, "distributed context: use cal_set_matrix_csr_dist");
     const int64_t nnz = rowptr[n];
@@ -1444,6 +1558,7 @@ int cal_set_matrix_csc(cal_ctx* c, int64_t n, const int64_t* jc, const int64_t* 
     // y(i) in sparse mtimes (column by column), so y is bit-identical to A*v.
     // For a symmetric A the result equals the CSC arrays read as CSR.
     if (!c || n < 0 || !jc) return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csc: bad arguments");
+    CAL_TRY(shared_format_only_stacked(c, "cal_set_matrix_csc"));
     if (n >= ((int64_t)1 << 31)) return set_error(c, CAL_ERR_UNSUPPORTED, "n and nnz must be < 2^31 per rank");
     if (jc[0] != 0) return set_error(c, CAL_ERR_ARG, "column pointers must start at 0");
     for (int64_t j = 0; j < n; ++j)
@@ -1480,10 +1595,16 @@ int cal_set_diagonal(cal_ctx* c, int64_t n, const double* d) {
     if (!d || n != c->A.n_local) return set_error(c, CAL_ERR_ARG, "cal_set_diagonal: need d with n_local entries");
     for (int64_t i = 0; i < n; ++i)
         if (!std::isfinite(d[i])) return set_error(c, CAL_ERR_ARG, "cal_set_diagonal: non-finite entry in d");
+    if (c->A.shared)  // the two halves share one slot
+        for (int64_t i = 0; i < c->A.n_half; ++i)
+            if (d[i] != d[c->A.n_half + i])
+                return set_error(c, CAL_ERR_ARG, "cal_set_diagonal: the \"shared\" format stores one diagonal for both "
+                                                 "halves of blkdiag(H, H): d[i] must equal d[n + i]");
     CAL_TRY(diag_positions(c));  // refusals leave the matrix untouched
     CAL_TRY(ensure_scratch(c, (size_t)n));
     CAL_HIP(c, hipMemcpyAsync(c->d_scratch, d, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_TRY(diag_update_dev(c, c->d_scratch, n, 1, 0, nullptr, 0, nullptr));
+    if (c->A.shared) CAL_TRY(diag_update_dev(c, c->d_scratch, c->A.n_half, 2, 0, nullptr, 0, nullptr));
+    else CAL_TRY(diag_update_dev(c, c->d_scratch, n, 1, 0, nullptr, 0, nullptr));
     CAL_HIP(c, hipStreamSynchronize(c->stream));  // d is the caller's
     return 0;
 }
@@ -1509,7 +1630,8 @@ int cal_set_spmv_format(cal_ctx* c, const char* fmt) {
     else if (!strcmp(fmt, "csr")) c->spmv_format = 1;
     else if (!strcmp(fmt, "pattern")) c->spmv_format = 2;
     else if (!strcmp(fmt, "split")) c->spmv_format = 3;
-    else return set_error(c, CAL_ERR_ARG, "spmv format must be auto, csr, pattern or split");
+    else if (!strcmp(fmt, "shared")) c->spmv_format = 4;
+    else return set_error(c, CAL_ERR_ARG, "spmv format must be auto, csr, pattern, split or shared");
     return 0;
 }
 
@@ -1548,6 +1670,16 @@ int cal_spmv_split_info(cal_ctx* c, int* on, int64_t* P, int* H, int* neg1) {
     if (P) *P = s ? c->A.ds_P : 0;
     if (H) *H = s ? c->A.ds_H : 0;
     if (neg1) *neg1 = s && c->A.ds_neg1 ? 1 : 0;
+    return 0;
+}
+
+int cal_spmv_shared_info(cal_ctx* c, int* on, int64_t* n_half, int64_t* nnz_stored) {
+    if (!c) return CAL_ERR_ARG;
+    if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    const bool s = c->A.shared;
+    if (on) *on = s ? 1 : 0;
+    if (n_half) *n_half = s ? c->A.n_half : 0;
+    if (nnz_stored) *nnz_stored = s ? c->A.nnz : 0;
     return 0;
 }
 

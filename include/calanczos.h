@@ -77,7 +77,11 @@ int cal_set_matrix_csr(cal_ctx* ctx, int64_t n, const int64_t* rowptr, const int
  * handed to cal_set_matrix_csr: the real form of a complex problem whose
  * vectors are stacked, Re in rows [0, n), Im in rows [n, 2n) (the time
  * propagator, cal_prop_*).  Each half keeps H's rows, column offsets and row
- * patterns; the values are stored twice.  cal_matrix_info reports 2n. */
+ * patterns; the values are stored twice.  cal_matrix_info reports 2n.
+ * With the "shared" format selected (cal_set_spmv_format) H alone is uploaded
+ * and nothing is doubled: one copy of rowptr / col / val serves both halves
+ * (2n < 2^31 and nnz(H) < 2^31; one rank).  cal_matrix_info still reports the
+ * logical matrix, 2n rows and 2 nnz(H); cal_spmv_shared_info what is stored. */
 int cal_set_matrix_csr_stacked(cal_ctx* ctx, int64_t n, const int64_t* rowptr, const int32_t* colind,
                                const double* val);
 /* Row-slab of a distributed matrix: rows [row0, row0+nlocal) of the global
@@ -127,7 +131,7 @@ int cal_mpk_schedule(cal_ctx* ctx, int* schedule);
 int cal_powers_launches(cal_ctx* ctx, int* launches);
 /* Device storage of A, chosen at the next cal_set_matrix_*: "auto" (default:
  * row patterns when A has <= 65535 distinct rows of <= 32 entries, else
- * CSR), "csr", "pattern" or "split".  All are lossless and give bit-identical
+ * CSR), "csr", "pattern", "split" or "shared".  All are lossless and give bit-identical
  * SpMV results (same per-row summation order).
  * "split" forces the diagonal-split format for grid Hamiltonians H = K +
  * diag(V): a uniform 5- or 7-slot stencil K (offsets -P .. -1, 0, +1 .. +P, P
@@ -137,8 +141,24 @@ int cal_powers_launches(cal_ctx* ctx, int* launches);
  * not qualify.  "auto" takes it for a qualifying matrix that would otherwise
  * run on CSR or on the row / pair kernels; "csr" never does.  Everything but
  * the SpMV (residuals, normest's rescale) runs on the matrix's CSR copy, and
- * cal_spmv_format keeps reporting CSR for it. */
+ * cal_spmv_format keeps reporting CSR for it.
+ * "shared" (opt-in, never chosen by "auto") is the stacked matrix blkdiag(H, H)
+ * of cal_set_matrix_csr_stacked with H stored once: its SpMV (modes 0, 1, 2 and
+ * the fused Lanczos step) loads every col / val entry once and applies it to
+ * both halves, each row summed in the stacked CSR kernel's order -- y is
+ * bit-identical to the stacked "csr" context.  With it selected every other
+ * cal_set_matrix_* and a communicator of several ranks return
+ * CAL_ERR_UNSUPPORTED (the message names cal_set_matrix_csr_stacked); it never
+ * falls back to another storage.  On a shared matrix whatever reads the CSR
+ * rows of the whole matrix returns CAL_ERR_UNSUPPORTED and names "csr" as the
+ * way to get it: normest (orth 'periodic' / 'selective'), the Ritz residuals
+ * (diagnostics, cal_compute_ritz_rnorm) and the restart drivers.
+ * cal_set_diagonal needs d[i] == d[n + i] there (CAL_ERR_ARG otherwise: the
+ * halves share one slot).  cal_spmv_format reports CSR for it. */
 int cal_set_spmv_format(cal_ctx* ctx, const char* fmt);
+/* The shared stacked format of the resident matrix: *on = 1 when H is stored
+ * once, with H's row count and stored nonzeros; zeros otherwise. */
+int cal_spmv_shared_info(cal_ctx* ctx, int* on, int64_t* n_half, int64_t* nnz_stored);
 /* The diagonal-split format of the resident matrix: *on = 1 when its SpMV
  * runs there, with the plane stride P, the in-plane reach H and *neg1 = 1
  * when every off-diagonal is -1; zeros otherwise. */

@@ -14,6 +14,10 @@ each in a fresh child process, alternating, --rounds times each:
   split  Context(spmv_format="split")
   csr    Context(spmv_format="csr")         the A/B partner
   lap    laplacian_3d(N), format "auto"     the plane march, the yardstick
+  shared Context(spmv_format="shared").set_matrix_stacked(H): blkdiag(H, H) with
+         H stored once -- every leg (spmv, lanczos, prop; no ca) on the 2n rows
+  csr2   Context(spmv_format="csr").set_matrix_stacked(H): the stacked CSR
+         matrix, shared's A/B partner, same legs on the same 2n rows
 A child measures, in --windows (>= 5) windows each after a warm-up:
   spmv     mode 0 back to back, 50 launches per window, each bracketed by the
            library's device events (cal_bench_spmv): mean us per launch;
@@ -33,7 +37,10 @@ class over 10 driven steps) and its rate over the bytes the library counts,
 is what the drive replaces, set_matrix_stacked of the new H (the diagonal
 rewritten in the host's CSR copy) before every step, 2 steps per window.
 --package-root DIR adds the undriven prop leg from another checkout's built
-package ("VARIANT@root", e.g. the parent commit's, to show it unchanged).
+package ("VARIANT@root", e.g. the parent commit's, to show it unchanged); for
+csr2 it adds every leg (the parent's stacked CSR, which shared is held against:
+"shared_vs_parent" says whether shared's median lies below the parent leg's
+fastest window), and none for shared, which the parent does not have.
 The summary has median, min and max over all windows of a variant and, for
 split against csr, whether split is faster beyond the spread of both (split's
 slowest window under csr's fastest).  --library runs the children on another
@@ -54,6 +61,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 S, BLOCKS = 8, 3
+STACKED = ("shared", "csr2")  # variants whose spmv / lanczos legs run on blkdiag(H, H)
 SPMV_PER_WINDOW, CA_PER_WINDOW, LZ_PER_WINDOW, PROP_PER_WINDOW = 50, 10, 100, 4
 
 
@@ -79,18 +87,26 @@ def child(a):
     N, W = a.N, a.windows
     A = build(cal, np, a.variant, N)
     n = A.shape[0]
-    fmt = {"split": "split", "csr": "csr", "lap": "auto"}[a.variant]
-    ctx = cal.Context(spmv_format=fmt).set_matrix(A)
+    fmt = {"split": "split", "csr": "csr", "lap": "auto", "shared": "shared", "csr2": "csr"}[a.variant]
+    stacked = a.variant in STACKED
+    ctx = cal.Context(spmv_format=fmt)
+    if stacked:
+        ctx.set_matrix_stacked(A)
+        n = 2 * n  # the legs below run on the stacked problem
+    else:
+        ctx.set_matrix(A)
     out = dict(variant=a.variant, library=os.path.basename(_lib.LIB_PATH), package=os.path.relpath(os.path.dirname(cal.__file__), ROOT),
                drive=a.drive, n=n, nnz=int(A.nnz),
                spmv_format=ctx.spmv_format(), plane_info=ctx.spmv_plane_info(), split_info=ctx.spmv_split_info())
+    if hasattr(ctx, "spmv_shared_info"):
+        out["shared_info"] = ctx.spmv_shared_info()
     only = a.only.split(",")
     if "spmv" in only:
         ctx.bench_spmv(20)
         out["spmv_us"] = [1e3 * ctx.bench_spmv(SPMV_PER_WINDOW)[0] for _ in range(W)]
         out["spmv_launches"] = W * SPMV_PER_WINDOW
     r = np.random.default_rng(0).standard_normal(n)
-    if "ca" in only:
+    if "ca" in only and not stacked:
         wu = 3
         ctx.lanczos_begin(r, S, wu + W * CA_PER_WINDOW + 1, "newton", "local")
         for _ in range(wu):
@@ -124,6 +140,7 @@ def child(a):
         out["lanczos_fused"] = info["fused"]
     ctx.close()
     if "prop" in only:
+        n = A.shape[0]
         idx = np.arange(n)
         coords = [(idx // N ** d) % N for d in range(3)]
         r2 = sum((c - 0.5 * (N - 1)) ** 2 for c in coords)
@@ -205,7 +222,8 @@ def run_child(a, variant, drive="0", root=None):
     if a.library:
         env["CAL_LIBRARY"] = a.library
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--variant", variant, "--N", str(a.N),
-           "--windows", str(a.windows), "--only", a.only if drive == "0" and not root else "prop", "--dt", str(a.dt),
+           "--windows", str(a.windows), "--only", a.only if drive == "0" and (not root or variant in STACKED) else "prop",
+           "--dt", str(a.dt),
            "--drive", drive]
     if root:
         cmd += ["--package-root", root]
@@ -244,7 +262,7 @@ def main():
     legs = [(v, v, "0", None) for v in variants] if "0" in drives else []
     legs += [("%s+drive%s" % (v, d), v, d, None) for v in variants if v != "lap" for d in drives if d != "0"]
     if a.package_root:
-        legs += [("%s@root" % v, v, "0", a.package_root) for v in variants]
+        legs += [("%s@root" % v, v, "0", a.package_root) for v in variants if v != "shared"]
     variants = [l[0] for l in legs]
     res = dict(N=a.N, n=a.N ** 3, rounds=a.rounds, windows=a.windows, only=a.only, library=a.library or "production",
                s=S, blocks=BLOCKS, runs={v: [] for v in variants})
@@ -275,12 +293,24 @@ def main():
             per_row = 33.0 if v == "split" else 25.0  # algorithmic bytes per row of the marches
             nnz = res["runs"][v][0]["nnz"]
             b = per_row * n if v != "csr" else 12.0 * nnz + 20.0 * n
+            if v.split("@")[0] == "csr2":
+                b = 2.0 * (12.0 * nnz + 20.0 * n)
+            if v == "shared":
+                b = 12.0 * nnz + 4.0 * (n + 1) + 32.0 * n
             summ[v]["spmv"]["algorithmic_TBps"] = b / (summ[v]["spmv"]["median"] * 1e-6) / 1e12
     if "split" in summ and "csr" in summ:
         res["split_vs_csr"] = {
             k: dict(ratio=summ["csr"][k]["median"] / summ["split"][k]["median"],
                     beyond_spread=bool(summ["split"][k]["max"] < summ["csr"][k]["min"]))
             for k in summ["split"] if k in summ["csr"]}
+    for name, other in (("shared_vs_csr2", "csr2"), ("shared_vs_parent", "csr2@root"),
+                        ("shared_vs_csr2_driven", "csr2+drive1")):
+        mine = "shared+drive1" if other.endswith("drive1") else "shared"
+        if mine in summ and other in summ:
+            res[name] = {
+                k: dict(ratio=summ[other][k]["median"] / summ[mine][k]["median"],
+                        median_below_fastest_window=bool(summ[mine][k]["median"] < summ[other][k]["min"]))
+                for k in ("spmv", "lanczos", "prop") if k in summ[mine] and k in summ[other]}
     if "split" in summ and "lap" in summ:
         res["split_over_lap_time"] = {k: summ["split"][k]["median"] / summ["lap"][k]["median"]
                                       for k in summ["split"] if k in summ["lap"]}
