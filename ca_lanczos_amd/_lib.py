@@ -161,6 +161,8 @@ SIGNATURES = [
     ("cal_prop_set_drive", c_int, [c_void_p, c_int, dp]),
     ("cal_prop_step_driven", c_int, [c_void_p, c_double, c_double, c_int, c_int, dp, c_int]),
     ("cal_prop_refresh_shifts", c_int, [c_void_p]),
+    ("cal_prop_set_nonlinear", c_int, [c_void_p, c_double, c_char_p]),
+    ("cal_prop_get_nonlinear", c_int, [c_void_p, c_int64, c_int64, dp, POINTER(c_int64)]),
     ("cal_ca_lanczos_prop", c_int,
      [c_void_p, c_int64, dp, dp, c_int, c_int, c_double, c_double, c_char_p, dp, c_int, c_int, dp, dp, dp, ip]),
     ("cal_lanczos", c_int, [c_void_p, dp, c_int, c_char_p, c_int, dp, dp, dp, dp, POINTER(StdLanczosInfo)]),

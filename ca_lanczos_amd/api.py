@@ -1010,7 +1010,13 @@ class Propagator:
         ``a_{1,2} = 1/2 +- sqrt(3)/3`` -- two rows of amplitudes (and two
         history rows of the observables) per step through the same call.
         ``self.t`` advances by the sub-steps' sum.  ``drive=None`` is the
-        undriven call: it steps under whatever H the last driven step left."""
+        undriven call: it steps under whatever H the last driven step left.
+
+        After ``set_nonlinear`` every (sub-)step is a nonlinear step.
+        ``scheme`` keeps its meaning for the drive: under "cf4" each of the
+        two sub-steps is a nonlinear step of its own, so the drive is treated
+        to fourth order while the nonlinear part stays second order
+        ("midpoint" density) or first ("frozen")."""
         if drive is None:
             st = check(self.ctx.h, lib.cal_prop_step(self.ctx.h, float(dt), float(tol), 1 if adaptive else 0,
                                                      int(nsteps)), "prop_step")
@@ -1038,6 +1044,38 @@ class Propagator:
         check(self.ctx.h, lib.cal_prop_set_drive(self.ctx.h, nk, ptr(Wm) if nk else None), "prop_set_drive")
         self._nk = nk
         return self
+
+    def set_nonlinear(self, g, density="midpoint"):
+        """The Gross-Pitaevskii term: from now on ``step`` propagates
+        ``i d/dt psi = (H0 + drive + g |psi|^2) psi``.  The diagonal is formed
+        from the state on the device before each Krylov build (one launch
+        with the drive; no copy back).  ``density="frozen"`` uses
+        ``|psi_n|^2`` for the whole step (first order, one build per step);
+        ``"midpoint"`` predicts ``psi*`` with a frozen step and then steps
+        from ``psi_n`` under ``g (|psi_n|^2 + |psi*|^2)/2`` (second order, two
+        builds per step).  ``g = 0`` switches the term off; H0's diagonal goes
+        back when neither the term nor a drive is set.  Clears ``nonlinear()``.
+        Not built: the conserved Gross-Pitaevskii energy as an observable
+        (``energy`` stays ``<psi|H|psi>`` with the H stored in the matrix)
+        and more than second order in the nonlinear part."""
+        if not getattr(self, "_open", False):
+            raise CalError(_lib.CAL_ERR_ARG, "set_nonlinear: the propagator is closed")
+        check(self.ctx.h, lib.cal_prop_set_nonlinear(self.ctx.h, float(g), str(density).encode()),
+              "prop_set_nonlinear")
+        return self
+
+    def nonlinear(self, first=0, count=None):
+        """One row ``[t_n, sum_i |psi_n,i|^4]`` per completed step since
+        ``set_nonlinear`` (rows [first, first + count); default all), psi_n
+        the state the step started from: ``g/2`` times the second column is
+        the interaction energy.  Shape (rows, 2)."""
+        nr = ctypes.c_int64()
+        check(self.ctx.h, lib.cal_prop_get_nonlinear(self.ctx.h, 0, 0, None, ctypes.byref(nr)), "prop_get_nonlinear")
+        count = nr.value - first if count is None else count
+        rows = np.zeros((max(count, 0), 2))
+        check(self.ctx.h, lib.cal_prop_get_nonlinear(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr)),
+              "prop_get_nonlinear")
+        return rows
 
     def refresh_shifts(self):
         """Forget the Newton shifts of the first step: the next step computes

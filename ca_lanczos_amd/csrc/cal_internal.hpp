@@ -601,6 +601,26 @@ struct DiagDrive {
     double* ds_diag = nullptr;
 };
 hipError_t launch_diag_drive(const DiagDrive& a, hipStream_t st);
+// k_diag_density: k_diag_drive's diagonal plus a nonlinear term of one state
+// A = ua + i va (B null) or of two (B = ub + i vb), each a stacked device
+// vector (Re in [0, n), Im in [n, 2n)); for i < n, every product and sum
+// rounded separately,
+//   ra = ua*ua;  ra = ra + va*va;  rb = ub*ub;  rb = rb + vb*vb   (rb: B only)
+//   d = V0[i];  for k ascending:  p = f[k] * W[i + k ldw];  d = d + p
+//   p = ga*ra;  d = d + p;  p = gb*rb;  d = d + p                 (gb: B only)
+// then k_diag_drive's stores of d, and q = ra*ra summed over the block's rows
+// (wave tree, the four waves in order) into partial[block], block <
+// diag_density_blocks(n): launch_reduce(partial, blocks, 1, ...) gives
+// sum_i |A_i|^4.  One launch writes the drive and the density together.
+struct DiagDensity {
+    DiagDrive d;
+    const double* A = nullptr;
+    const double* B = nullptr;  // null: one state
+    double ga = 0.0, gb = 0.0;
+    double* partial = nullptr;
+};
+int diag_density_blocks(int64_t n);
+hipError_t launch_diag_density(const DiagDensity& a, hipStream_t st);
 
 
 }  // namespace cal
@@ -932,6 +952,13 @@ int diag_positions(cal_ctx* c);
 // format, ds_diag; enqueued on the stream, no host wait once the positions exist
 int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
                     const double* f);
+// diag_update_dev with the nonlinear term of launch_diag_density in the same
+// launch: H's diagonal <- V0 + sum_k f[k] W(:, k) + ga |A|^2 (+ gb |B|^2, B
+// non-null), A / B stacked device states of 2n doubles; the blocks' shares of
+// sum_i |A_i|^4 go to partial (diag_density_blocks(n) doubles, the caller's).
+// Same positions, same rule for a shared matrix, timed as the drive is.
+int diag_density_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
+                     const double* f, const double* A_dev, double ga, const double* B_dev, double gb, double* partial);
 // dst[i] = val[dpos[i]], i < cnt <= n_local (device dst; enqueued)
 int diag_gather_dev(cal_ctx* c, double* dst, int64_t cnt);
 int allreduce_sum(cal_ctx* c, double* d_buf, int64_t count);

@@ -18,6 +18,13 @@
 // (cal_prop_set_drive / cal_prop_step_driven) rewrites the matrix's stored
 // diagonal in place before each step (prop.hip k_diag_drive through
 // runtime.cpp diag_update_dev): the step itself is unchanged.
+// A nonlinear term g |psi|^2 (cal_prop_set_nonlinear; Gross-Pitaevskii) adds
+// the state's density to that diagonal on the device (prop.hip k_diag_density
+// through runtime.cpp diag_density_dev, the drive in the same launch): once
+// per step with the density of psi_n ("frozen", first order), or twice
+// ("midpoint": a frozen step predicts psi* into a second buffer, then the step
+// proper runs from psi_n under the mean of both densities; second order, two
+// Krylov builds, no copy of the state).
 // An absorbing mask (cal_prop_set_absorber) multiplies the state by a real
 // diagonal 0 <= M <= 1 at the end of every step, inside the combine sweep
 // (prop.hip's ABS flag), and records the squared norm it removes.
@@ -75,6 +82,19 @@ struct PropState {
     double* d_mask = nullptr;    // ldm doubles
     int64_t ldm = 0;             // roundup(n, 64)
     std::vector<double> ahist;
+    // the nonlinear term g |psi|^2 (cal_prop_set_nonlinear): the diagonal is
+    // V0 + the drive + the density of the state, rewritten by one
+    // k_diag_density launch before every Krylov build.  V0 (d_v0) belongs to
+    // the first of {drive, term} set and goes back when the last goes off.
+    double g = 0.0;              // 0: off
+    bool nl_mid = false;         // "midpoint" (two builds per step); false: "frozen"
+    double* d_psi2 = nullptr;    // midpoint's predicted state (A.ld doubles, pad rows zero)
+    double* h_coef2 = nullptr;   // pinned; the predictor's coefficients (2 kPropMaxCols)
+    double* d_nlpart = nullptr;  // the density kernel's block shares of sum |psi_n|^4 (nl_nb), reduced by the
+    int nl_nb = 0;               // step's combine (d_partial is the Lanczos blocks' in between)
+    double f_last[kDriveMaxOps] = {0.0, 0.0, 0.0, 0.0};  // the amplitudes of the most recent driven step
+    std::vector<double> nhist;   // one row [t_n, sum |psi_n|^4] per completed step since the set
+    bool nl_on() const { return g != 0.0; }
     bool obs_on() const { return nw > 0 || nphi > 0 || energy; }
     bool abs_on() const { return d_mask != nullptr; }
     int nq() const { return nw + 2 * nphi; }
@@ -84,6 +104,9 @@ struct PropState {
     int red_absorbed() const { return 1 + nq(); }
     int red_energy() const { return 1 + nq() + (abs_on() ? 1 : 0); }
     int red_count() const { return red_energy() + (energy ? 1 : 0); }
+    // the most a step brings back: red_count() at its largest (the norm, nw + 2 nphi sums at their caps, the
+    // absorbed norm, the energy) and the nonlinear term's sum after it -- the size of h_coef's tail
+    static constexpr int kRedMax = 1 + 3 * kPropMaxObs + 1 + 1 + 1;
     double* psi(const cal_ctx* c) const { return d_psi + c->A.lpad; }
 };
 
@@ -143,19 +166,76 @@ void obs_free(PropState& P) {
     P.hist.clear();
 }
 
-// switch the drive off: V0 back into the matrix it was taken from (when that
-// matrix is still the context's), then the copies are freed
-int drive_off(cal_ctx* c, PropState& P) {
-    int st = 0;
-    if (P.d_v0 && c->has_A && c->A_gen == P.drv_gen && c->A.n_local == 2 * P.n) {
-        st = diag_update_dev(c, P.d_v0, P.n, 2, 0, nullptr, 0, nullptr);
-        if (hipStreamSynchronize(c->stream) != hipSuccess && st == 0) st = CAL_ERR_HIP;
+// V0 is still the diagonal of the context's matrix underneath what was written
+bool v0_current(const cal_ctx* c, const PropState& P) {
+    return P.d_v0 && c->has_A && c->A_gen == P.drv_gen && c->A.n_local == 2 * P.n;
+}
+
+// V0 + sum_k f[k] W_k (f null: V0 alone) back into the matrix V0 was taken
+// from, when that matrix is still the context's; waits for it
+int v0_write(cal_ctx* c, PropState& P, const double* f) {
+    if (!v0_current(c, P)) return 0;
+    int st = f ? diag_update_dev(c, P.d_v0, P.n, 2, P.nk, P.d_drv, P.ldd, f)
+               : diag_update_dev(c, P.d_v0, P.n, 2, 0, nullptr, 0, nullptr);
+    if (hipStreamSynchronize(c->stream) != hipSuccess && st == 0) st = CAL_ERR_HIP;
+    return st;
+}
+
+// the propagator takes the diagonal: V0 <- the matrix's, as it is now (a V0
+// taken from a matrix that is no longer the context's is dropped first)
+int v0_take(cal_ctx* c, PropState& P) {
+    if (P.d_v0 && !v0_current(c, P)) {
+        hipFree(P.d_v0);
+        P.d_v0 = nullptr;
     }
-    if (P.d_v0) hipFree(P.d_v0);
+    if (P.d_v0) return 0;
+    CAL_HIP(c, hipMalloc((void**)&P.d_v0, P.n * sizeof(double)));
+    int st = diag_gather_dev(c, P.d_v0, P.n);
+    if (st == 0 && hipStreamSynchronize(c->stream) != hipSuccess)
+        st = set_error(c, CAL_ERR_HIP, "cal_prop: gathering the diagonal failed");
+    if (st < 0) {
+        hipFree(P.d_v0);
+        P.d_v0 = nullptr;
+        return st;
+    }
+    P.drv_gen = c->A_gen;
+    return 0;
+}
+
+// the drive's operators are freed (the matrix is not touched)
+void drive_free(PropState& P) {
     if (P.d_drv) hipFree(P.d_drv);
-    P.d_v0 = P.d_drv = nullptr;
+    P.d_drv = nullptr;
     P.nk = 0;
     P.ldd = 0;
+    for (double& f : P.f_last) f = 0.0;
+}
+
+// the nonlinear term's buffers are freed (the matrix is not touched)
+void nl_free(PropState& P) {
+    if (P.d_psi2) hipFree(P.d_psi2);
+    if (P.d_nlpart) hipFree(P.d_nlpart);
+    if (P.h_coef2) hipHostFree(P.h_coef2);
+    P.d_psi2 = P.d_nlpart = P.h_coef2 = nullptr;
+    P.nl_nb = 0;
+    P.g = 0.0;
+    P.nl_mid = false;
+    P.nhist.clear();
+}
+
+// the last of {drive, nonlinear term} went off: V0 back into the matrix, then it is freed
+int v0_release(cal_ctx* c, PropState& P) {
+    const int st = v0_write(c, P, nullptr);
+    if (P.d_v0) hipFree(P.d_v0);
+    P.d_v0 = nullptr;
+    return st;
+}
+
+// everything that owns the diagonal goes off
+int drive_off(cal_ctx* c, PropState& P) {
+    const int st = v0_release(c, P);
+    drive_free(P);
+    nl_free(P);
     return st;
 }
 
@@ -200,13 +280,15 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     const int nd = dot_blocks(2 * P.n);
     const size_t pe = (size_t)nk * nb;  // the energy's partials follow the combine's
     CAL_TRY(ensure_partial(c, pe + (P.energy ? (size_t)std::max(P.eparts, nd) : 0)));
-    CAL_TRY(ensure_red(c, (size_t)P.red_count()));
+    const int nred = P.red_count() + (P.nl_on() ? 1 : 0);  // the nonlinear term's sum |psi_n|^4 comes last
+    CAL_TRY(ensure_red(c, (size_t)nred));
     k.partial = c->d_partial;
     const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n + (double)P.n * (nk - 1)) * 8.0);
     const hipError_t e = launch_prop_combine(k, c->stream);
     timer_end(c, t);
     if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
     CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, nk, c->d_red, c->stream));
+    if (P.nl_on()) CAL_HIP_OTHER(c, launch_reduce(P.d_nlpart, P.nl_nb, 1, c->d_red + P.red_count(), c->stream));
     if (P.energy) {
         // <psi'|H|psi'> = y'x over the stacked rows, y = blkdiag(H, H) x: the
         // fused Lanczos mode's dot, reduced as lanczos_std.cpp reduces it
@@ -223,11 +305,44 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     }
     // everything reduced comes back with the squared norm in the one pinned transfer
     double* h = P.h_coef + 2 * kPropMaxCols;
-    CAL_HIP_OTHER(c, hipMemcpyAsync(h, c->d_red, (size_t)P.red_count() * sizeof(double), hipMemcpyDeviceToHost,
-                                    c->stream));
+    CAL_HIP_OTHER(c, hipMemcpyAsync(h, c->d_red, (size_t)nred * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     CAL_HIP(c, hipStreamSynchronize(c->stream));
     P.nrm2 = h[0];
     return 0;
+}
+
+// the predictor's combine: d_psi2 <- Q(:, 0:m) (a + i b), the plain sweep (no
+// observables, no mask), nothing reduced and no host wait -- the corrector's
+// density launch follows it on the stream.  The coefficients are staged in
+// h_coef2: h_coef is the step proper's.
+int combine_predict_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, const double* a,
+                        const double* b) {
+    std::memcpy(P.h_coef2, a, m * sizeof(double));
+    std::memcpy(P.h_coef2 + kPropMaxCols, b, m * sizeof(double));
+    CAL_HIP_OTHER(c, hipMemcpyAsync(P.d_coef, P.h_coef2, 2 * kPropMaxCols * sizeof(double), hipMemcpyHostToDevice,
+                                    c->stream));
+    PropCombine k;
+    k.Q = Q;
+    k.ld = ld;
+    k.n = P.n;
+    k.m = m;
+    k.a = P.d_coef;
+    k.b = P.d_coef + kPropMaxCols;
+    k.out = P.d_psi2 + c->A.lpad;
+    const int nb = prop_combine_blocks(P.n);
+    CAL_TRY(ensure_partial(c, (size_t)nb));
+    k.partial = c->d_partial;  // the provisional state's norm is not used
+    const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n) * 8.0);
+    const hipError_t e = launch_prop_combine(k, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
+    return 0;
+}
+
+// the diagonal <- V0 + sum_k f[k] W_k + ga |psi_n|^2 (+ gb |B|^2), one launch;
+// the blocks' shares of sum |psi_n|^4 stay in d_nlpart for the step's combine
+int density_dev(cal_ctx* c, PropState& P, const double* f, double ga, const double* B, double gb) {
+    return diag_density_dev(c, P.d_v0, P.n, 2, P.nk, P.d_drv, P.ldd, f, P.psi(c), ga, B, gb, P.d_nlpart);
 }
 
 // the history row of the step just completed (combine_dev's transfer is in h_coef)
@@ -593,8 +708,9 @@ static int prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double*
     const int64_t ld = c->A.ld;
     CAL_HIP(c, hipMalloc((void**)&P->d_psi, ld * sizeof(double)));
     CAL_HIP(c, hipMalloc((void**)&P->d_coef, 2 * kPropMaxCols * sizeof(double)));
-    CAL_HIP(c, hipHostMalloc((void**)&P->h_coef, (2 * kPropMaxCols + 16) * sizeof(double), hipHostMallocDefault));
-    std::memset(P->h_coef, 0, (2 * kPropMaxCols + 16) * sizeof(double));
+    CAL_HIP(c, hipHostMalloc((void**)&P->h_coef, (2 * kPropMaxCols + PropState::kRedMax) * sizeof(double),
+                             hipHostMallocDefault));
+    std::memset(P->h_coef, 0, (2 * kPropMaxCols + PropState::kRedMax) * sizeof(double));
     CAL_HIP(c, hipMemsetAsync(P->d_psi, 0, ld * sizeof(double), c->stream));
     CAL_HIP(c, hipMemcpyAsync(P->psi(c), psi_re, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (psi_im)
@@ -624,7 +740,11 @@ int cal_prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* ps
 
 // nsteps time steps; f non-null: before step `it` the diagonal is set to
 // V0 + sum_k f[it ldf + k] W_k (one k_diag_drive launch, enqueued ahead of the
-// step's first kernel on the same stream)
+// step's first kernel on the same stream).  With a nonlinear term on, that
+// launch is k_diag_density's instead (the drive and g |psi|^2 together, once
+// per Krylov build: twice per step under "midpoint"), and it runs for f null
+// too, with the amplitudes of the most recent driven step (f_last; zeros
+// before the first)
 static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int adaptive, int nsteps, const double* f,
                       int ldf) {
     const std::string w = who;
@@ -646,14 +766,43 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
     const double t0 = now_ms();
     std::vector<double> cre, cim;
     int status = 0;
+    if (P.nl_on() && (!P.d_v0 || c->A_gen != P.drv_gen))
+        return set_error(c, CAL_ERR_ARG, w + ": the context's matrix changed since cal_prop_set_nonlinear");
     for (int it = 0; it < nsteps; ++it) {
-        if (f) {
-            status = diag_update_dev(c, P.d_v0, P.n, 2, P.nk, P.d_drv, P.ldd, f + (size_t)it * ldf);
-            if (status < 0) break;
-        }
+        if (f)
+            for (int k = 0; k < P.nk; ++k) P.f_last[k] = f[(size_t)it * ldf + k];
         const double nrm = std::sqrt(P.nrm2);
         int kuse = 0;
         double resid = 0.0;
+        if (P.nl_on()) {
+            // the drive and the density of psi_n in one launch; "midpoint" then
+            // predicts psi* into d_psi2 (psi_n and its norm stay where they
+            // are) and rewrites the diagonal with the mean of both densities
+            status = density_dev(c, P, P.f_last, P.g, nullptr, 0.0);
+            if (status < 0) break;
+            if (P.nl_mid) {
+                status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid);
+                if (status < 0) break;
+                if (kuse == 0) {  // the state is unchanged
+                    status = set_error(c, CAL_WARN_BREAKDOWN, w + ": the predictor's first CA block broke down");
+                    break;
+                }
+                const int kp = kuse * P.s;
+                for (int j = 0; j < kp; ++j) {
+                    cre[j] = nrm * cre[j];
+                    cim[j] = nrm * cim[j];
+                }
+                const LanczosView vp = lanczos_view(c);
+                status = combine_predict_dev(c, P, vp.Q, vp.ld, kp, cre.data(), cim.data());
+                if (status < 0) break;
+                status = density_dev(c, P, P.f_last, 0.5 * P.g, P.d_psi2 + c->A.lpad, 0.5 * P.g);
+                if (status < 0) break;
+                kuse = 0;
+            }
+        } else if (f) {
+            status = diag_update_dev(c, P.d_v0, P.n, 2, P.nk, P.d_drv, P.ldd, f + (size_t)it * ldf);
+            if (status < 0) break;
+        }
         status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid);
         if (status < 0) break;
         if (kuse == 0) {  // the state is unchanged
@@ -668,6 +817,10 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
         const LanczosView v = lanczos_view(c);
         status = combine_dev(c, P, v.Q, v.ld, ks, cre.data(), cim.data());
         if (status < 0) break;
+        if (P.nl_on()) {  // [t_n, sum |psi_n|^4]: the state the step started from
+            P.nhist.push_back(P.t);
+            P.nhist.push_back(P.h_coef[2 * kPropMaxCols + P.red_count()]);
+        }
         P.t += dt;
         if (P.obs_on()) record_row(P);
         if (P.abs_on()) record_absorbed(P);
@@ -702,24 +855,88 @@ int cal_prop_set_drive(cal_ctx* c, int nk, const double* W) {
     for (size_t i = 0; i < (size_t)nk * P.n; ++i)
         if (!std::isfinite(W[i])) return set_error(c, CAL_ERR_ARG, "cal_prop_set_drive: non-finite entry in W");
     CAL_TRY(diag_positions(c));  // refusals leave the matrix and an earlier drive as they are
-    CAL_TRY(drive_off(c, P));    // an earlier drive: its V0 goes back first
-    if (nk == 0) return 0;
-    P.ldd = pad64(P.n);
-    P.drv_gen = c->A_gen;
-    CAL_HIP(c, hipMalloc((void**)&P.d_v0, P.n * sizeof(double)));
-    CAL_HIP(c, hipMalloc((void**)&P.d_drv, (size_t)nk * P.ldd * sizeof(double)));
-    int st = diag_gather_dev(c, P.d_v0, P.n);
-    if (st == 0 && (upload_cols(c, P.d_drv, P.ldd, W, P.n, nk) < 0 ||
+    // an earlier drive goes off: V0 goes back into the matrix, and stays the
+    // propagator's while a nonlinear term is on (the matrix then holds V0 + g
+    // rho: gathering it again would take the wrong values)
+    int st = P.nl_on() ? v0_write(c, P, nullptr) : v0_release(c, P);
+    drive_free(P);
+    if (st < 0 || nk == 0) return st;
+    CAL_TRY(v0_take(c, P));
+    const int64_t ldd = pad64(P.n);
+    double* d = nullptr;
+    if (hipMalloc((void**)&d, (size_t)nk * ldd * sizeof(double)) != hipSuccess) st = CAL_ERR_HIP;
+    if (st == 0 && (upload_cols(c, d, ldd, W, P.n, nk) < 0 ||
                     hipStreamSynchronize(c->stream) != hipSuccess))  // W is the caller's
-        st = set_error(c, CAL_ERR_HIP, "cal_prop_set_drive: upload failed");
-    if (st < 0) {  // nothing was written to the matrix yet
-        hipFree(P.d_v0);
-        hipFree(P.d_drv);
-        P.d_v0 = P.d_drv = nullptr;
-        P.ldd = 0;
-        return st;
+        st = CAL_ERR_HIP;
+    if (st < 0) {  // the matrix holds V0
+        if (d) hipFree(d);
+        if (!P.nl_on()) v0_release(c, P);
+        return set_error(c, CAL_ERR_HIP, "cal_prop_set_drive: upload failed");
     }
+    P.d_drv = d;
+    P.ldd = ldd;
     P.nk = nk;
+    return 0;
+}
+
+int cal_prop_set_nonlinear(cal_ctx* c, double g, const char* density) {
+    if (!c) return CAL_ERR_ARG;
+    CAL_TRY(active_prop(c, "cal_prop_set_nonlinear", true));
+    hipSetDevice(c->device);
+    PropState& P = *c->prop;
+    const std::string dn = density ? density : "";
+    if (!std::isfinite(g)) return set_error(c, CAL_ERR_ARG, "cal_prop_set_nonlinear: g must be finite");
+    if (dn != "frozen" && dn != "midpoint")
+        return set_error(c, CAL_ERR_ARG, "cal_prop_set_nonlinear: density must be \"frozen\" or \"midpoint\"");
+    if (g == 0.0) {
+        if (!P.nl_on()) return 0;  // nothing was set: nothing to put back
+        CAL_HIP(c, hipStreamSynchronize(c->stream));
+        nl_free(P);
+        // a drive stays: the matrix goes back to whatever H its last step left
+        return P.nk > 0 ? v0_write(c, P, P.f_last) : v0_release(c, P);
+    }
+    CAL_TRY(diag_positions(c));  // refusals leave the matrix and the propagator as they are
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    const bool owned = P.d_v0 != nullptr;
+    CAL_TRY(v0_take(c, P));  // the first of {drive, term}: V0 is gathered now
+    if (!P.d_psi2) {
+        const int64_t ld = c->A.ld;
+        const int nb = diag_density_blocks(P.n);
+        double *psi2 = nullptr, *part = nullptr, *h2 = nullptr;
+        if (hipMalloc((void**)&psi2, ld * sizeof(double)) != hipSuccess ||
+            hipMalloc((void**)&part, (size_t)nb * sizeof(double)) != hipSuccess ||
+            hipHostMalloc((void**)&h2, 2 * kPropMaxCols * sizeof(double), hipHostMallocDefault) != hipSuccess ||
+            hipMemsetAsync(psi2, 0, ld * sizeof(double), c->stream) != hipSuccess ||
+            hipMemsetAsync(part, 0, (size_t)nb * sizeof(double), c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) {
+            if (psi2) hipFree(psi2);
+            if (part) hipFree(part);
+            if (h2) hipHostFree(h2);
+            if (!owned) v0_release(c, P);  // nothing else was written
+            return set_error(c, CAL_ERR_HIP, "cal_prop_set_nonlinear: allocation failed");
+        }
+        std::memset(h2, 0, 2 * kPropMaxCols * sizeof(double));
+        P.d_psi2 = psi2;
+        P.d_nlpart = part;
+        P.h_coef2 = h2;
+        P.nl_nb = nb;
+    }
+    P.g = g;
+    P.nl_mid = dn == "midpoint";
+    P.nhist.clear();
+    return 0;
+}
+
+int cal_prop_get_nonlinear(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows) {
+    if (!c) return CAL_ERR_ARG;
+    CAL_TRY(active_prop(c, "cal_prop_get_nonlinear", false));
+    const PropState& P = *c->prop;
+    const int64_t nr = (int64_t)(P.nhist.size() / 2);
+    if (nrows) *nrows = nr;
+    if (!out) return 0;
+    if (first < 0 || count < 0 || first + count > nr)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_get_nonlinear: rows [first, first + count) out of range");
+    std::memcpy(out, P.nhist.data() + (size_t)first * 2, (size_t)count * 2 * sizeof(double));
     return 0;
 }
 

@@ -439,6 +439,62 @@ __global__ __launch_bounds__(kDiagThreads) void k_diag_drive(DiagDrive a) {
         }
 }
 
+// k_diag_density: k_diag_drive with the nonlinear term g |psi|^2 of one state
+// (TWO = false) or of two (TWO = true: the midpoint rule's average of the
+// densities of psi_n and the predicted psi*).  One row per lane, 8-byte
+// accesses only (the lower half of a state starts at row n, which may be odd),
+// the order of cal_internal.hpp's DiagDensity:
+//   ra = ua*ua;  ra = ra + va*va;  [rb likewise]  the drive's chain into d;
+//   p = ga*ra;  d = d + p;  [p = gb*rb;  d = d + p]  the drive's stores
+// and the lane's q = ra*ra (0 past row n) summed as everything else here:
+// wave tree, the four waves in order, one partial per block.  No lane leaves
+// before the barrier.
+template <bool SPLIT, bool TWO>
+__global__ __launch_bounds__(kDiagThreads) void k_diag_density(DiagDensity a) {
+    __shared__ double ws[kDiagThreads / 64];
+    const int64_t n = a.d.n;
+    const int64_t i = (int64_t)blockIdx.x * kDiagThreads + threadIdx.x;
+    double acc = 0.0;
+    if (i < n) {
+        const double ua = a.A[i], va = a.A[n + i];
+        double ra = ua * ua;
+        ra = ra + va * va;
+        double rb = 0.0;
+        if (TWO) {
+            const double ub = a.B[i], vb = a.B[n + i];
+            rb = ub * ub;
+            rb = rb + vb * vb;
+        }
+        double d = a.d.V0[i];
+#pragma unroll
+        for (int k = 0; k < kDriveMaxOps; ++k)
+            if (k < a.d.nk) {
+                const double p = a.d.f[k] * a.d.W[k * a.d.ldw + i];
+                d = d + p;
+            }
+        double p = a.ga * ra;
+        d = d + p;
+        if (TWO) {
+            p = a.gb * rb;
+            d = d + p;
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (h < a.d.halves) {
+                const int64_t r = i + h * n;
+                a.d.val[a.d.dpos[r]] = d;
+                if (SPLIT) a.d.ds_diag[r] = d;
+            }
+        const double q = ra * ra;
+        acc = acc + q;
+    }
+    acc = prop_wave_sum(acc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) ws[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
 }  // namespace
 
 int diag_find_blocks(int64_t n) {
@@ -461,6 +517,29 @@ hipError_t launch_diag_drive(const DiagDrive& a, hipStream_t st) {
     const dim3 grid((unsigned)((a.n + kDiagThreads - 1) / kDiagThreads)), block(kDiagThreads);
     if (a.ds_diag) hipLaunchKernelGGL(k_diag_drive<true>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(k_diag_drive<false>, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+int diag_density_blocks(int64_t n) {
+    const int64_t b = (n + kDiagThreads - 1) / kDiagThreads;
+    return (int)(b < 1 ? 1 : b);
+}
+
+hipError_t launch_diag_density(const DiagDensity& a, hipStream_t st) {
+    const DiagDrive& d = a.d;
+    if (d.n < 1 || d.n >= ((int64_t)1 << 31) || d.halves < 1 || d.halves > 2 || d.nk < 0 || d.nk > kDriveMaxOps)
+        return hipErrorInvalidValue;
+    if (!d.V0 || !d.dpos || !d.val || (d.nk > 0 && (!d.W || d.ldw < d.n))) return hipErrorInvalidValue;
+    if (!a.A || !a.partial) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)diag_density_blocks(d.n)), block(kDiagThreads);
+    auto launch = [&](auto k) { hipLaunchKernelGGL(k, grid, block, 0, st, a); };
+    if (d.ds_diag) {
+        if (a.B) launch(k_diag_density<true, true>);
+        else launch(k_diag_density<true, false>);
+    } else {
+        if (a.B) launch(k_diag_density<false, true>);
+        else launch(k_diag_density<false, false>);
+    }
     return hipGetLastError();
 }
 

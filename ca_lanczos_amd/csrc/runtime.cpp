@@ -913,6 +913,44 @@ int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int
     return 0;
 }
 
+int diag_density_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
+                     const double* f, const double* A_dev, double ga, const double* B_dev, double gb, double* partial) {
+    CAL_TRY(diag_positions(c));
+    DevMatrix& A = c->A;
+    if (halves < 1 || halves > 2 || n < 1 || n * halves != A.n_local || nk < 0 || nk > kDriveMaxOps || !V0_dev ||
+        (nk > 0 && (!W_dev || !f || ldw < n)) || !A_dev || !partial)
+        return set_error(c, CAL_ERR_ARG, "diag_density_dev: bad arguments");
+    if (A.shared) {  // both halves read one slot: it is written once, on H's rows
+        if (halves != 2)
+            return set_error(c, CAL_ERR_ARG, "diag_density_dev: a shared matrix takes both halves at once");
+        halves = 1;
+    }
+    DiagDensity a;
+    a.d.V0 = V0_dev;
+    a.d.W = W_dev;
+    a.d.ldw = ldw;
+    a.d.n = n;
+    a.d.nk = nk;
+    a.d.halves = halves;
+    for (int k = 0; k < nk; ++k) a.d.f[k] = f[k];
+    a.d.dpos = A.dpos;
+    a.d.val = A.val;
+    a.d.ds_diag = A.use_dsplit ? A.ds_diag : nullptr;
+    a.A = A_dev;
+    a.B = B_dev;
+    a.ga = ga;
+    a.gb = B_dev ? gb : 0.0;
+    a.partial = partial;
+    // the drive's bytes and the 2n doubles of each state in; one partial per block out
+    const double bytes = (double)n * (8.0 * (1 + nk) + 4.0 * halves) + (double)n * halves * (A.use_dsplit ? 16.0 : 8.0) +
+                         (double)n * 16.0 * (B_dev ? 2 : 1) + 8.0 * diag_density_blocks(n);
+    const int t = timer_begin(c, 7, bytes);  // the drive's kind: the one launch that rewrites the diagonal
+    const hipError_t e = launch_diag_density(a, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_diag_density");
+    return 0;
+}
+
 int diag_gather_dev(cal_ctx* c, double* dst, int64_t cnt) {
     CAL_TRY(diag_positions(c));
     if (!dst || cnt < 0 || cnt > c->A.n_local) return set_error(c, CAL_ERR_ARG, "diag_gather_dev: bad arguments");

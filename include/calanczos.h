@@ -475,6 +475,53 @@ int cal_prop_step_driven(cal_ctx* ctx, double dt, double tol, int adaptive, int 
  * unnecessary for a drive small against it.  No-op for the monomial basis. */
 int cal_prop_refresh_shifts(cal_ctx* ctx);
 
+/* ---- a nonlinear term: i d/dt psi = (H0 + sum_k f_k(t) diag(W_k) + g |psi|^2) psi ---- */
+/* The Gross-Pitaevskii / nonlinear Schroedinger equation.  After this call
+ * cal_prop_step and cal_prop_step_driven take nonlinear steps: before a
+ * Krylov build one kernel forms the diagonal from the state on the device
+ * and writes it, with the drive, in one launch (no copy of the state to the
+ * host).  For row i, with A = ua + i va and (two states only) B = ub + i vb,
+ * every product and sum rounded separately, so a NumPy loop gives the bits:
+ *   ra = ua*ua;  ra = ra + va*va
+ *   rb = ub*ub;  rb = rb + vb*vb                                  (two states)
+ *   d  = V0[i];  for k ascending:  p = f_k*W_k[i];  d = d + p     (the drive's chain)
+ *   p  = ga*ra;  d = d + p
+ *   p  = gb*rb;  d = d + p                                        (two states)
+ * and d goes to row i's diagonal in both halves of blkdiag(H, H).
+ * density "frozen": ga = g, A = psi_n, one state; then the step is
+ *   cal_prop_step's.  First order in dt, one Krylov build per step.
+ * density "midpoint" (predictor-corrector, second order, two builds per step):
+ *   (a) a frozen step from psi_n to a provisional psi* (no observables, no
+ *       absorber, no history row; the time and info.steps do not advance);
+ *   (b) ga = gb = 0.5*g, A = psi_n, B = psi*;
+ *   (c) the step proper from psi_n, with everything that is set.
+ *   The same row of amplitudes f serves both passes.
+ * If a pass breaks down the call returns CAL_WARN_BREAKDOWN with the state
+ * psi_n unchanged.  cal_prop_info under "midpoint": breakdowns and
+ * rank_deficient count the blocks of both builds of a step; steps, lsteps,
+ * lsteps_max, lsteps_sum, residual and residual_max are the corrector's alone.  Under cal_prop_step the f_k are those of the most recent
+ * driven step (zeros before the first).  The propagator owns the diagonal
+ * from the first of {cal_prop_set_drive, cal_prop_set_nonlinear} to the last
+ * of them that goes off (g = 0, nk = 0, cal_prop_end, a new cal_prop_begin);
+ * then H0's diagonal is put back.  g = 0 with nothing set is a no-op.
+ * CAL_ERR_ARG for a NULL context, no active propagator, a non-finite g or a
+ * density other than the two; CAL_ERR_UNSUPPORTED as cal_prop_set_drive, with
+ * the matrix untouched.  Setting the term clears its history.
+ * Not built: the conserved Gross-Pitaevskii energy as an observable (the
+ * energy observable stays <psi'|H|psi'> with the H stored in the matrix:
+ * under "midpoint" H0 + drive + g (|psi_n|^2 + |psi*|^2)/2), and more than
+ * second order in the nonlinear part (a "cf4" drive's sub-steps are
+ * nonlinear steps each). */
+int cal_prop_set_nonlinear(cal_ctx* ctx, double g, const char* density);
+/* One row [t_n, sum_i |psi_n,i|^4] per completed step since the term was set,
+ * psi_n the state the step started from and t_n its time (g/2 times the sum
+ * is the interaction energy).  Summed by the density kernel: per row q =
+ * ra*ra, the rows of a 256-row block by a wave tree and the four waves in
+ * order, the blocks in the library's fixed order.  It arrives with the
+ * step's squared norm, in the same transfer.  out == NULL: only *nrows.
+ * Copies rows [first, first+count), two doubles each. */
+int cal_prop_get_nonlinear(cal_ctx* ctx, int64_t first, int64_t count, double* out, int64_t* nrows);
+
 /* [T,Q,lsteps] = ca_lanczos_prop(A,r0,s,m,dt,tol,basis,eigest,adaptive)
  * (ca_lanczos_prop.m:3-135) with r0 = r_re + i r_im (r_im may be NULL) on the
  * stacked matrix: T is *lsteps x *lsteps (ld *lsteps; room for s*m squared),

@@ -36,6 +36,15 @@ class over 10 driven steps) and its rate over the bytes the library counts,
 (8 (1 + NK) + 4 * 2) n in + 16 * 2 * n out (8 * 2 * n on CSR); "reupload"
 is what the drive replaces, set_matrix_stacked of the new H (the diagonal
 rewritten in the host's CSR copy) before every step, 2 steps per window.
+--nonlinear LIST (comma separated, e.g. frozen,midpoint,copyback) adds prop legs
+under the Gross-Pitaevskii term g |psi|^2 (g = 0.05; the start state's largest
+|psi|^2 is 1), each in a child of its own ("VARIANT+nlNAME"), undriven:
+"frozen" and "midpoint" are Propagator.set_nonlinear's two densities, where the
+child also reports the density kernel's own time (the "drive" timer class over
+10 steps: one launch per step "frozen", two "midpoint"); "copyback" is the
+route they replace -- state() back to the host, |psi|^2 and the new diagonal in
+NumPy, and a new Propagator on the rewritten matrix, every step (the frozen
+scheme; 2 steps per window).
 --package-root DIR adds the undriven prop leg from another checkout's built
 package ("VARIANT@root", e.g. the parent commit's, to show it unchanged); for
 csr2 it adds every leg (the parent's stacked CSR, which shared is held against:
@@ -63,6 +72,7 @@ sys.path.insert(0, ROOT)
 S, BLOCKS = 8, 3
 STACKED = ("shared", "csr2")  # variants whose spmv / lanczos legs run on blkdiag(H, H)
 SPMV_PER_WINDOW, CA_PER_WINDOW, LZ_PER_WINDOW, PROP_PER_WINDOW = 50, 10, 100, 4
+G_NL = 0.05  # the --nonlinear legs' coupling
 
 
 def build(cal, np, variant, N):
@@ -96,7 +106,7 @@ def child(a):
     else:
         ctx.set_matrix(A)
     out = dict(variant=a.variant, library=os.path.basename(_lib.LIB_PATH), package=os.path.relpath(os.path.dirname(cal.__file__), ROOT),
-               drive=a.drive, n=n, nnz=int(A.nnz),
+               drive=a.drive, nonlinear=a.nonlinear, n=n, nnz=int(A.nnz),
                spmv_format=ctx.spmv_format(), plane_info=ctx.spmv_plane_info(), split_info=ctx.spmv_split_info())
     if hasattr(ctx, "spmv_shared_info"):
         out["shared_info"] = ctx.spmv_shared_info()
@@ -179,6 +189,27 @@ def child(a):
                     Hn.data[dpos] = d0 + amp(P.t + 0.5 * a.dt)[0] * ops[0]
                     ctx.set_matrix_stacked(Hn)
                     P.step(a.dt, 1)
+        elif a.nonlinear in ("frozen", "midpoint"):
+            P.set_nonlinear(G_NL, a.nonlinear)
+
+            def steps(k):
+                P.step(a.dt, k)
+        elif a.nonlinear == "copyback":
+            per_window = 2
+            rows = np.repeat(np.arange(n), np.diff(A.indptr))
+            dpos = np.nonzero(rows == A.indices)[0]
+            del rows
+            d0 = A.data[dpos].copy()
+            Hn = A.copy()
+
+            def steps(k):
+                nonlocal P
+                for _ in range(k):
+                    psi = P.state()
+                    P.close()
+                    Hn.data[dpos] = d0 + G_NL * (psi.real ** 2 + psi.imag ** 2)
+                    P = cal.Propagator(Hn, psi, S, BLOCKS, basis="newton", ctx=ctx)
+                    P.step(a.dt, 1)
         else:
             def steps(k):
                 P.step(a.dt, k)
@@ -190,7 +221,7 @@ def child(a):
             steps(per_window)
             ctx.synchronize()
             ms.append(1e3 * (time.perf_counter() - t0) / per_window)
-        if nk > 0:  # the drive kernel alone: its own timer class over 10 driven steps
+        if nk > 0 or a.nonlinear in ("frozen", "midpoint"):  # the diagonal's kernel alone: its own timer class over 10 steps
             K = 10
             ctx.timer_enable(True)
             ctx.timer_reset()
@@ -215,21 +246,23 @@ def child(a):
     print(json.dumps(out))
 
 
-def run_child(a, variant, drive="0", root=None):
+def run_child(a, variant, drive="0", root=None, nonlinear="0"):
     env = dict(os.environ)
     env.pop("CAL_LIBRARY", None)
     env.pop("CAL_SPMV_FORMAT", None)
     if a.library:
         env["CAL_LIBRARY"] = a.library
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--variant", variant, "--N", str(a.N),
-           "--windows", str(a.windows), "--only", a.only if drive == "0" and (not root or variant in STACKED) else "prop",
+           "--windows", str(a.windows), "--only",
+           a.only if drive == "0" and nonlinear == "0" and (not root or variant in STACKED) else "prop",
            "--dt", str(a.dt),
-           "--drive", drive]
+           "--drive", drive, "--nonlinear", nonlinear]
     if root:
         cmd += ["--package-root", root]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
     if p.returncode != 0:
-        raise RuntimeError("child %s drive %s failed (%d): %s" % (variant, drive, p.returncode, p.stderr[-2000:]))
+        raise RuntimeError("child %s drive %s nonlinear %s failed (%d): %s"
+                           % (variant, drive, nonlinear, p.returncode, p.stderr[-2000:]))
     return json.loads(p.stdout.strip().splitlines()[-1])
 
 
@@ -243,6 +276,7 @@ def main():
     ap.add_argument("--dt", type=float, default=0.05)
     ap.add_argument("--library", default=None)
     ap.add_argument("--drive", default="0", help="prop leg: comma list of 0, 1..4 (operators) or reupload")
+    ap.add_argument("--nonlinear", default="0", help="prop leg: comma list of frozen, midpoint, copyback")
     ap.add_argument("--package-root", default=None, help="also the undriven prop leg from this checkout's package")
     ap.add_argument("--child-timeout", type=int, default=500)
     ap.add_argument("--variant", default=None, help=argparse.SUPPRESS)
@@ -259,16 +293,21 @@ def main():
     for d in drives:
         if d not in ("0", "1", "2", "3", "4", "reupload"):
             ap.error("--drive takes 0, 1..4 or reupload")
-    legs = [(v, v, "0", None) for v in variants] if "0" in drives else []
-    legs += [("%s+drive%s" % (v, d), v, d, None) for v in variants if v != "lap" for d in drives if d != "0"]
+    nls = [x for x in a.nonlinear.split(",") if x != "0"]
+    for x in nls:
+        if x not in ("frozen", "midpoint", "copyback"):
+            ap.error("--nonlinear takes frozen, midpoint or copyback")
+    legs = [(v, v, "0", None, "0") for v in variants] if "0" in drives else []
+    legs += [("%s+drive%s" % (v, d), v, d, None, "0") for v in variants if v != "lap" for d in drives if d != "0"]
+    legs += [("%s+nl%s" % (v, x), v, "0", None, x) for v in variants if v != "lap" for x in nls]
     if a.package_root:
-        legs += [("%s@root" % v, v, "0", a.package_root) for v in variants if v != "shared"]
+        legs += [("%s@root" % v, v, "0", a.package_root, "0") for v in variants if v != "shared"]
     variants = [l[0] for l in legs]
     res = dict(N=a.N, n=a.N ** 3, rounds=a.rounds, windows=a.windows, only=a.only, library=a.library or "production",
                s=S, blocks=BLOCKS, runs={v: [] for v in variants})
     for i in range(a.rounds):  # alternating, each in a fresh process
-        for name, v, d, root in legs:
-            res["runs"][name].append(run_child(a, v, d, root))
+        for name, v, d, root, nl in legs:
+            res["runs"][name].append(run_child(a, v, d, root, nl))
             print("round %d: %s done" % (i + 1, name), file=sys.stderr, flush=True)
 
     keys = dict(spmv="spmv_us", ca="ca_ms_per_outer", lanczos="lanczos_ms_per_vector", prop="prop_ms_per_step")
@@ -284,7 +323,7 @@ def main():
         dk = [r["drive_kernel"] for r in res["runs"][v] if "drive_kernel" in r]
         if dk:
             summ[v]["drive_kernel"] = dict(us=statistics.median(x["us"] for x in dk), us_all=[x["us"] for x in dk],
-                                           bytes=dk[0]["bytes"],
+                                           bytes=dk[0]["bytes"], launches_per_step=dk[0]["launches_per_step"],
                                            TBps=dk[0]["bytes"] / (statistics.median(x["us"] for x in dk) * 1e-6) / 1e12)
     res["summary"] = summ
     n = a.N ** 3
