@@ -117,6 +117,8 @@ SIGNATURES = [
     ("cal_spmv_format", c_int, [c_void_p, ip, ip, ip]),
     ("cal_spmv_split_info", c_int, [c_void_p, ip, POINTER(c_int64), ip, ip]),
     ("cal_spmv_shared_info", c_int, [c_void_p, ip, POINTER(c_int64), POINTER(c_int64)]),
+    ("cal_set_matrix_csr_hermitian", c_int, [c_void_p, c_int64, POINTER(c_int64), POINTER(c_int32), dp, dp]),
+    ("cal_spmv_hermitian_info", c_int, [c_void_p, ip, POINTER(c_int64), POINTER(c_int64)]),
     ("cal_split_analyze", c_int, [c_int64, POINTER(c_int64), POINTER(c_int32), dp, POINTER(c_int64), ip, ip]),
     ("cal_bench_spmv", c_int, [c_void_p, c_int, c_double, dp, dp]),
     ("cal_spmv", c_int, [c_void_p, dp, dp]),

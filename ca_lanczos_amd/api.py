@@ -27,8 +27,9 @@ class Context:
 
     ``spmv_format`` (cal_set_spmv_format; default ``CAL_SPMV_FORMAT`` or
     "auto") is "auto", "csr", "pattern", "split" or "shared".  "shared" is
-    opt-in and takes ``set_matrix_stacked`` only: blkdiag(H, H) with H stored
-    once (``spmv_shared_info``)."""
+    opt-in and takes ``set_matrix_stacked`` (blkdiag(H, H) with H stored
+    once, ``spmv_shared_info``) and ``set_matrix_hermitian`` (a complex
+    Hermitian H stored once, ``spmv_hermitian_info``) only."""
 
     def __init__(self, device: int | None = None, spmv_format: str | None = None, orth_coef: str | None = None,
                  mpk_depth: int | None = None, normalize: str | None = None):
@@ -194,7 +195,7 @@ class Context:
         a complex problem on stacked vectors [Re; Im] (the time propagator).
         On a ``spmv_format="shared"`` context H is stored once and serves both
         halves (same bits as the stacked "csr" context); that format takes no
-        other way of setting a matrix."""
+        other way of setting a matrix but ``set_matrix_hermitian``."""
         H = to_csr(H)
         if H.shape[0] != H.shape[1]:
             raise ValueError("H must be square")
@@ -206,6 +207,40 @@ class Context:
             col.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(val)), "set_matrix_stacked")
         self.n = 2 * H.shape[0]
         return self
+
+    def set_matrix_hermitian(self, H):
+        """A complex Hermitian sparse H = A + iB through
+        cal_set_matrix_csr_hermitian: the real symmetric 2n x 2n matrix
+        E(H) = [[A, -B], [B, A]] on stacked vectors [Re; Im]
+        (``matrices.hermitian_embedding``), which the time propagator takes
+        as it takes ``set_matrix_stacked``'s.  ``H.data.real`` and
+        ``H.data.imag`` go down; a real dtype passes no imaginary part and is
+        ``set_matrix_stacked(H)``.  The stored diagonal must be real, and
+        Hermiticity of the rest is the caller's contract.  On a
+        ``spmv_format="shared"`` context H is stored once (20 bytes per
+        nonzero, ``spmv_hermitian_info``); any other format stores the
+        embedding, four entries per nonzero of H."""
+        H = to_csr(H)
+        if H.shape[0] != H.shape[1]:
+            raise ValueError("H must be square")
+        rowptr = np.ascontiguousarray(H.indptr, dtype=np.int64)
+        col = np.ascontiguousarray(H.indices, dtype=np.int32)
+        re = np.ascontiguousarray(H.data.real, dtype=np.float64)
+        im = np.ascontiguousarray(H.data.imag, dtype=np.float64) if np.iscomplexobj(H.data) else None
+        check(self.h, lib.cal_set_matrix_csr_hermitian(
+            self.h, H.shape[0], rowptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            col.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(re), ptr(im)), "set_matrix_hermitian")
+        self.n = 2 * H.shape[0]
+        return self
+
+    def spmv_hermitian_info(self):
+        """(on, n, nnz stored) of the Hermitian stored-once format
+        (``spmv_format="shared"`` with ``set_matrix_hermitian`` of a complex
+        H); (False, 0, 0) for any other matrix, the host-built embedding of
+        the other formats included."""
+        on, n, nz = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        check(self.h, lib.cal_spmv_hermitian_info(self.h, ctypes.byref(on), ctypes.byref(n), ctypes.byref(nz)))
+        return bool(on.value), n.value, nz.value
 
     def _prop_combine(self, Q, c, mask, W, phi, entry):
         """The marshalling of the three host-data combine entries; ``entry``
@@ -968,10 +1003,14 @@ def drive_rows(drive, t0, dt, nsteps, scheme="midpoint"):
 
 
 class Propagator:
-    """Time stepper ``psi <- exp(-i dt H) psi`` for a real symmetric sparse H
-    and a complex state (cal_prop_*; ca_lanczos_prop.m as runLanczos.m:84-131
-    drives it).  H is embedded as blkdiag(H, H) and the state lives on the
-    device as [Re psi; Im psi]; ``state()`` is the only copy back of the
+    """Time stepper ``psi <- exp(-i dt H) psi`` for a real symmetric or complex
+    Hermitian sparse H and a complex state (cal_prop_*; ca_lanczos_prop.m as
+    runLanczos.m:84-131 drives it).  A real H is embedded as blkdiag(H, H)
+    (``set_matrix_stacked``), a complex-dtype H = A + iB as [[A, -B], [B, A]]
+    (``set_matrix_hermitian``: magnetic fields, velocity gauge, rotating
+    frames); the state lives on the device as [Re psi; Im psi].  Observables,
+    energy, absorber, drive and the nonlinear term touch only the real
+    diagonal and work on either.  ``state()`` is the only copy back of the
     state, ``set_observables`` / ``observables`` watch it from the device."""
 
     def __init__(self, H, psi0, s, max_blocks, basis="newton", eigest=None, ctx=None):
@@ -982,7 +1021,10 @@ class Propagator:
         self._own = ctx is None
         self.ctx = ctx or Context()
         try:
-            self.ctx.set_matrix_stacked(H)
+            if np.iscomplexobj(H):
+                self.ctx.set_matrix_hermitian(H)
+            else:
+                self.ctx.set_matrix_stacked(H)
             re, im = _split(psi0)
             if re.shape[0] != self.n:
                 raise ValueError("psi0 must have H.shape[0] entries")

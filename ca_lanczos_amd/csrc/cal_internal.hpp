@@ -240,6 +240,13 @@ struct DevMatrix {
     // shared_refuses' callers may read the CSR arrays of such a matrix.
     bool shared = false;
     int64_t n_half = 0;
+    // The Hermitian stored-once format (cal_set_matrix_csr_hermitian
+    // on a "shared" context): the matrix is E(H) = [[A, -B], [B, A]] for the
+    // complex Hermitian H = A + iB.  A shared matrix in every other respect
+    // (shared stays true, val holds A with the real diagonal), plus vim: B's nnz
+    // values in val's order, written at the upload and never again.
+    bool herm = false;
+    double* vim = nullptr;
     // The stored diagonal's positions (runtime.cpp diag_positions; built at the
     // first cal_set_diagonal / cal_prop_set_drive, never at upload): val[dpos[r]]
     // is the entry of row r with col == r.  dpos_state: 0 not looked for, 1
@@ -271,6 +278,9 @@ hipError_t launch_spmv(const SpmvArgs& a, hipStream_t st);
 // blocks, the vectors have 2 n_half rows; modes 0, 1, 2 and 4 (mode 4 writes
 // 2 a.nblk partials: the top half's, then the bottom half's)
 hipError_t launch_spmv_shared(const SpmvArgs& a, int64_t n_half, hipStream_t st);
+// the Hermitian stored-once SpMV (k_spmv_herm): as launch_spmv_shared, with
+// a.val the real parts and vim the imaginary parts of H's nonzeros
+hipError_t launch_spmv_herm(const SpmvArgs& a, const double* vim, int64_t n_half, hipStream_t st);
 hipError_t launch_spmv_pat(const PatArgs& a, hipStream_t st);
 // mode 4's grid = its number of y'x partials (0: this storage has no fused
 // Lanczos mode -- the row-pattern kernels k_spmv_pat / k_spmv_pat_lds)
@@ -789,11 +799,13 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
                   const std::vector<int>& col, const double* val);
 // The "shared" format's upload (cal_set_matrix_csr_stacked): H alone, n rows,
 // as the matrix blkdiag(H, H) of 2n rows (DevMatrix::shared).
+// vim non-null: the Hermitian stored-once matrix E(H), H = val + i vim
+// (cal_set_matrix_csr_hermitian; DevMatrix::herm).
 int upload_matrix_shared(cal_ctx* c, int64_t n, const std::vector<int>& rowptr, const std::vector<int>& col,
-                         const double* val);
+                         const double* val, const double* vim = nullptr);
 // The one place that decides what a shared matrix refuses: 0 for any other
-// matrix; on a shared one CAL_ERR_UNSUPPORTED, with a message that names `what`
-// and the "csr" format.  Every reader of A.rowptr / col / val / blk / nblk other
+// matrix; on a shared one CAL_ERR_UNSUPPORTED, with a message that names `what`,
+// the "csr" format and the setter that was used.  Every reader of A.rowptr / col / val / blk / nblk other
 // than the shared SpMV and the diagonal helpers asks it first, so nothing
 // indexes rowptr past H's n_half rows.
 int shared_refuses(cal_ctx* c, const char* what);

@@ -14,6 +14,9 @@
 //                   partials of y'x (lanczos.m:103-107; lz_sub, lz_block_sum).
 //   k_spmv_shared   the same on blkdiag(H, H) with H stored once: one load of
 //                   col / val, two gathers, two products, both halves' rows.
+//   k_spmv_herm     the same on [[A, -B], [B, A]] for a complex Hermitian
+//                   H = A + iB stored once: one more value per nonzero, the
+//                   two gathers cross-mixed.
 //   k_spmv_pat_lds, k_spmv_pair
 //                   row-pattern SpMV (lossless pattern table, one / two rows
 //                   per lane), same arithmetic, same shift epilogue; the pair
@@ -450,6 +453,162 @@ hipError_t launch_spmv_shared(const SpmvArgs& a, int64_t n_half, hipStream_t st)
         case 1: return launch_spmv_shared_mode<1>(a, nh, nit, st);
         case 2: return a.xprev ? launch_spmv_shared_mode<2>(a, nh, nit, st) : hipErrorInvalidValue;
         case 4: return a.dotp ? launch_spmv_shared_mode<4>(a, nh, nit, st) : hipErrorInvalidValue;
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// --------------------------------------------------------------------------
+// The Hermitian stored-once SpMV: y = E(H) x with E(H) =
+// [[A, -B], [B, A]] for the complex Hermitian H = A + iB, H stored once (a.val
+// = A's values, vim = B's, one col / rowptr).  Grid, row blocks, thread <-> row,
+// the epilogues and MODE 4's partial layout are k_spmv_shared's; a nonzero
+// loads one more value and cross-mixes its two gathers x0 = x[c], x1 = x[nh + c]:
+//     top half's term     a*x0 - b*x1
+//     bottom half's term  b*x0 + a*x1
+// with every product and the difference / sum rounded on its own (the file is
+// built -ffp-contract=off; herm_term spells the temporaries out).  Each row sums
+// its terms in stored order from +0.0 (tests/herm_ref.py herm_chain restates it).
+__device__ __forceinline__ void herm_term(double a, double b, double x0, double x1, double& pt, double& pb) {
+    const double t0 = a * x0, t1 = b * x1;
+    const double u0 = b * x0, u1 = a * x1;
+    pt = t0 - t1;
+    pb = u0 + u1;
+}
+
+template <int MODE, int NIT, bool NT>
+__global__ __launch_bounds__(kSpmvThreads) void k_spmv_herm(SpmvArgs a, const double* vim, int nh) {
+    static_assert(MODE == 0 || MODE == 1 || MODE == 2 || MODE == 4, "k_spmv_herm: modes 0, 1, 2 and 4");
+    __shared__ SharedProd prod;
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tid = threadIdx.x;
+    const int r0 = a.blk[b], r1 = a.blk[b + 1];
+    const int p0 = a.rowptr[r0], p1 = a.rowptr[r1];
+    const int cnt = p1 - p0;
+    const double* xb = a.x + nh;  // the bottom half
+    const bool lzhas = MODE == 4 && a.xprev && a.pb2;
+    const double lzb = lzhas ? sqrt(*a.pb2) : 0.0;
+    const double* lzq = lzhas ? a.xprev : a.x;
+    double lzd0 = 0.0, lzd1 = 0.0;  // MODE 4: the thread's y * x, per half
+    if (cnt <= kSpmvNnz) {
+        if (cnt > 0) {
+            // all col / val / vim loads (clamped, unbranched), then both gathers
+            // of every nonzero, then the LDS terms
+            const int pl = p1 - 1;
+            int ci[NIT];
+            double vr[NIT], vi[NIT], x0[NIT], x1[NIT];
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int p = min(p0 + it * kSpmvThreads + tid, pl);
+                ci[it] = ldnt<NT>(a.col + p);
+                vr[it] = ldnt<NT>(a.val + p);
+                vi[it] = ldnt<NT>(vim + p);
+            }
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                x0[it] = a.x[ci[it]];
+                x1[it] = xb[ci[it]];
+            }
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int q = it * kSpmvThreads + tid;
+                double pt, pb;
+                herm_term(vr[it], vi[it], x0[it], x1[it], pt, pb);
+                if (q < cnt) prod.put(q, pt, pb);
+            }
+        }
+        __syncthreads();
+        const int r = r0 + tid;
+        if (r < r1) {
+            const int q0 = a.rowptr[r] - p0, q1 = a.rowptr[r + 1] - p0;
+            double s0 = 0.0, s1 = 0.0;
+            for (int j = q0; j < q1; ++j) prod.add(j, s0, s1);
+            if (MODE == 4) {
+                const double y0 = lz_sub(s0, lzb, lzq[r], lzhas);
+                const double y1 = lz_sub(s1, lzb, lzq[nh + r], lzhas);
+                a.y[r] = y0;
+                a.y[nh + r] = y1;
+                lzd0 = y0 * a.x[r];
+                lzd1 = y1 * xb[r];
+            } else {
+                a.y[r] = spmv_epilogue<MODE>(s0, a, r);
+                a.y[nh + r] = spmv_epilogue<MODE>(s1, a, nh + r);
+            }
+        }
+    } else {
+        // one long row (> kSpmvNnz nonzeros): chunked, both sums still in order
+        double s0 = 0.0, s1 = 0.0;
+        for (int c = p0; c < p1; c += kSpmvNnz) {
+            const int m = min(kSpmvNnz, p1 - c);
+            for (int q = tid; q < m; q += kSpmvThreads) {
+                const int cc = a.col[c + q];
+                double pt, pb;
+                herm_term(a.val[c + q], vim[c + q], a.x[cc], xb[cc], pt, pb);
+                prod.put(q, pt, pb);
+            }
+            __syncthreads();
+            if (tid == 0)
+                for (int j = 0; j < m; ++j) prod.add(j, s0, s1);
+            __syncthreads();
+        }
+        if (tid == 0) {  // the one thread that holds the row's sums
+            if (MODE == 4) {
+                const double y0 = lz_sub(s0, lzb, lzq[r0], lzhas);
+                const double y1 = lz_sub(s1, lzb, lzq[nh + r0], lzhas);
+                a.y[r0] = y0;
+                a.y[nh + r0] = y1;
+                lzd0 = y0 * a.x[r0];
+                lzd1 = y1 * xb[r0];
+            } else {
+                a.y[r0] = spmv_epilogue<MODE>(s0, a, r0);
+                a.y[nh + r0] = spmv_epilogue<MODE>(s1, a, nh + r0);
+            }
+        }
+    }
+    if constexpr (MODE == 4) {
+        // as k_spmv_shared: the wave sums reuse the products' LDS (32 KiB, five blocks per CU)
+        __syncthreads();
+        double* ws = reinterpret_cast<double*>(&prod);
+        const double t0 = lz_block_sum<kSpmvThreads / 64>(lzd0, ws);
+        const double t1 = lz_block_sum<kSpmvThreads / 64>(lzd1, ws + kSpmvThreads / 64);
+        if (tid == 0) {
+            a.dotp[b] = t0;
+            a.dotp[gridDim.x + b] = t1;
+        }
+    }
+}
+
+template <int MODE, bool NT>
+static hipError_t launch_spmv_herm_nit(const SpmvArgs& a, const double* vim, int nh, int nit, hipStream_t st) {
+    dim3 g(a.nblk), b(kSpmvThreads);
+    switch (nit) {
+        case 1: hipLaunchKernelGGL((k_spmv_herm<MODE, 1, NT>), g, b, 0, st, a, vim, nh); break;
+        case 2: hipLaunchKernelGGL((k_spmv_herm<MODE, 2, NT>), g, b, 0, st, a, vim, nh); break;
+        case 3: hipLaunchKernelGGL((k_spmv_herm<MODE, 3, NT>), g, b, 0, st, a, vim, nh); break;
+        case 4: hipLaunchKernelGGL((k_spmv_herm<MODE, 4, NT>), g, b, 0, st, a, vim, nh); break;
+        case 5: hipLaunchKernelGGL((k_spmv_herm<MODE, 5, NT>), g, b, 0, st, a, vim, nh); break;
+        case 6: hipLaunchKernelGGL((k_spmv_herm<MODE, 6, NT>), g, b, 0, st, a, vim, nh); break;
+        case 7: hipLaunchKernelGGL((k_spmv_herm<MODE, 7, NT>), g, b, 0, st, a, vim, nh); break;
+        default: hipLaunchKernelGGL((k_spmv_herm<MODE, 8, NT>), g, b, 0, st, a, vim, nh); break;
+    }
+    return hipGetLastError();
+}
+
+template <int MODE>
+static hipError_t launch_spmv_herm_mode(const SpmvArgs& a, const double* vim, int nh, int nit, hipStream_t st) {
+    return a.nt ? launch_spmv_herm_nit<MODE, true>(a, vim, nh, nit, st)
+                : launch_spmv_herm_nit<MODE, false>(a, vim, nh, nit, st);
+}
+
+// as launch_spmv_shared; vim: the imaginary parts of H's nonzeros, in a.val's order
+hipError_t launch_spmv_herm(const SpmvArgs& a, const double* vim, int64_t n_half, hipStream_t st) {
+    if (a.nblk <= 0) return hipSuccess;
+    if (!vim || n_half < 1 || 2 * n_half >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const int nit = (a.mode >> 8) & 0xff, nh = (int)n_half;
+    switch (a.mode & 0xff) {
+        case 0: return launch_spmv_herm_mode<0>(a, vim, nh, nit, st);
+        case 1: return launch_spmv_herm_mode<1>(a, vim, nh, nit, st);
+        case 2: return a.xprev ? launch_spmv_herm_mode<2>(a, vim, nh, nit, st) : hipErrorInvalidValue;
+        case 4: return a.dotp ? launch_spmv_herm_mode<4>(a, vim, nh, nit, st) : hipErrorInvalidValue;
         default: return hipErrorInvalidValue;
     }
 }

@@ -554,6 +554,70 @@ int cal_set_matrix_csr_stacked(cal_ctx* c, int64_t n, const int64_t* rowptr, con
     return cal_set_matrix_csr(c, 2 * n, rp.data(), col.data(), v.data());
 }
 
+// E(H) = [[A, -B], [B, A]] for the complex Hermitian H = A + iB (val_re, val_im):
+// the real symmetric matrix whose SpMV on [Re psi; Im psi] is [Re H psi; Im H psi].
+int cal_set_matrix_csr_hermitian(cal_ctx* c, int64_t n, const int64_t* rowptr, const int32_t* colind,
+                                 const double* val_re, const double* val_im) {
+    // a real H: blkdiag(H, H), cal_set_matrix_csr_stacked's own path and bits
+    if (!val_im) return cal_set_matrix_csr_stacked(c, n, rowptr, colind, val_re);
+    if (!c || n < 0 || !rowptr || (n > 0 && rowptr[n] > 0 && (!colind || !val_re)))
+        return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csr_hermitian: bad arguments");
+    const int64_t nnz = rowptr[n];
+    const bool shared = c->spmv_format == 4;
+    if (shared && c->comm && c->comm->nranks > 1)
+        return set_error(c, CAL_ERR_UNSUPPORTED, "cal_set_matrix_csr_hermitian: the \"shared\" format runs on one "
+                                                 "rank (the context has a communicator of several ranks)");
+    if (shared && (nnz < 0 || nnz >= ((int64_t)1 << 31) || 2 * n >= ((int64_t)1 << 31)))
+        return set_error(c, CAL_ERR_UNSUPPORTED, "cal_set_matrix_csr_hermitian: 2n and nnz(H) must be < 2^31");
+    if (!shared && (nnz < 0 || 4 * nnz >= ((int64_t)1 << 31) || 2 * n >= ((int64_t)1 << 31)))
+        return set_error(c, CAL_ERR_UNSUPPORTED, "cal_set_matrix_csr_hermitian: 2n and 4 nnz(H) must be < 2^31 "
+                                                 "(the embedding [[A, -B], [B, A]] stores every nonzero four times)");
+    if (shared && n < 1)
+        return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csr_hermitian: the \"shared\" format needs n >= 1");
+    if (rowptr[0] != 0) return set_error(c, CAL_ERR_ARG, "row pointers must start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (rowptr[i + 1] < rowptr[i]) return set_error(c, CAL_ERR_ARG, "row pointers must be non-decreasing");
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t p = rowptr[i]; p < rowptr[i + 1]; ++p) {
+            if (colind[p] < 0 || colind[p] >= n) return set_error(c, CAL_ERR_ARG, "column index out of range");
+            if (colind[p] == i && val_im[p] != 0.0)  // NaN too
+                return set_error(c, CAL_ERR_ARG, "cal_set_matrix_csr_hermitian: the diagonal of a Hermitian matrix is "
+                                                 "real (a stored diagonal entry has a non-zero imaginary part)");
+        }
+    if (shared) {
+        // H alone goes up: rowptr / col / val as for blkdiag(H, H), plus the imaginary parts
+        hipSetDevice(c->device);
+        std::vector<int> rp(n + 1), col(colind, colind + nnz);
+        for (int64_t i = 0; i <= n; ++i) rp[i] = (int)rowptr[i];
+        return upload_matrix_shared(c, n, rp, col, val_re, val_im);
+    }
+    // any other format: the embedding on the host, explicit zeros kept (the
+    // pattern does not depend on the values).  Top row i: (c, a) in stored
+    // order, then (n + c, -b); bottom row n + i: (c, b), then (n + c, a).
+    std::vector<int64_t> rp(2 * n + 1);
+    std::vector<int32_t> col(4 * nnz);
+    std::vector<double> v(4 * nnz);
+    rp[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t p0 = rowptr[i], k = rowptr[i + 1] - p0, t = 2 * p0, b = 2 * nnz + 2 * p0;
+        rp[i + 1] = t + 2 * k;
+        rp[n + i + 1] = b + 2 * k;
+        for (int64_t j = 0; j < k; ++j) {
+            const int32_t cj = colind[p0 + j];
+            const double ar = val_re[p0 + j], bi = val_im[p0 + j];
+            col[t + j] = cj;
+            v[t + j] = ar;
+            col[t + k + j] = (int32_t)(cj + n);
+            v[t + k + j] = -bi;
+            col[b + j] = cj;
+            v[b + j] = bi;
+            col[b + k + j] = (int32_t)(cj + n);
+            v[b + k + j] = ar;
+        }
+    }
+    return cal_set_matrix_csr(c, 2 * n, rp.data(), col.data(), v.data());
+}
+
 int cal_prop_combine(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
                      double* out_re, double* out_im, double* norm2) {
     if (!c) return CAL_ERR_ARG;

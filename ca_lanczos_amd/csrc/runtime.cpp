@@ -211,6 +211,7 @@ static void free_matrix(cal_ctx* c) {
     if (A.ds_gsum) hipFree(A.ds_gsum);
     if (A.ds_dprod) hipFree(A.ds_dprod);
     if (A.dpos) hipFree(A.dpos);
+    if (A.vim) hipFree(A.vim);
     A = DevMatrix();
     if (c->d_work) hipFree(c->d_work);
     c->d_work = nullptr;
@@ -754,14 +755,15 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
 // stacked CSR upload gives, so everything above the SpMV sees the same 2n-row
 // problem; the row blocks and nit are H's.  Never another storage.
 int upload_matrix_shared(cal_ctx* c, int64_t n, const std::vector<int>& rowptr, const std::vector<int>& col,
-                         const double* val) {
+                         const double* val, const double* vim) {
     free_matrix(c);
     DevMatrix& A = c->A;
     A.shared = true;
+    A.herm = vim != nullptr;  // E(H) of H = val + i vim: one more array, everything else H's
     A.n_half = n;
     A.n_local = A.n_global = A.n_rows = 2 * n;
     A.nnz = rowptr[n];         // stored
-    A.nnz_loc = 2 * A.nnz;     // of the matrix the context represents
+    A.nnz_loc = (A.herm ? 4 : 2) * A.nnz;  // of the matrix the context represents
     A.lpad = 0;
     A.ld = ((2 * n + 2 + 63) / 64) * 64;  // upload_matrix's, for 2n rows
     if (A.ld == 0) A.ld = 64;
@@ -779,6 +781,10 @@ int upload_matrix_shared(cal_ctx* c, int64_t n, const std::vector<int>& rowptr, 
         CAL_HIP(c, hipMemcpy(A.col, col.data(), A.nnz * sizeof(int), hipMemcpyHostToDevice));
         CAL_HIP(c, hipMemcpy(A.val, val, A.nnz * sizeof(double), hipMemcpyHostToDevice));
     }
+    if (A.herm) {
+        CAL_HIP(c, hipMalloc((void**)&A.vim, std::max<int64_t>(A.nnz, 1) * sizeof(double)));
+        if (A.nnz > 0) CAL_HIP(c, hipMemcpy(A.vim, vim, A.nnz * sizeof(double), hipMemcpyHostToDevice));
+    }
     CAL_HIP(c, hipMemcpy(A.blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
     c->has_A = true;
     c->A_gen++;
@@ -787,17 +793,21 @@ int upload_matrix_shared(cal_ctx* c, int64_t n, const std::vector<int>& rowptr, 
 
 int shared_refuses(cal_ctx* c, const char* what) {
     if (!c->has_A || !c->A.shared) return 0;
+    const bool h = c->A.herm;
     return set_error(c, CAL_ERR_UNSUPPORTED,
                      std::string(what) + " reads the stored rows of the whole matrix, and the \"shared\" format stores "
-                                         "H of blkdiag(H, H) once: select the \"csr\" format (cal_set_spmv_format) "
-                                         "before cal_set_matrix_csr_stacked to get it");
+                                         "H of " + (h ? "[[A, -B], [B, A]]" : "blkdiag(H, H)") +
+                                         " once: select the \"csr\" format (cal_set_spmv_format) before " +
+                                         (h ? "cal_set_matrix_csr_hermitian" : "cal_set_matrix_csr_stacked") +
+                                         " to get it");
 }
 
 int shared_format_only_stacked(cal_ctx* c, const char* who) {
     if (c->spmv_format != 4) return 0;
     return set_error(c, CAL_ERR_UNSUPPORTED,
                      std::string(who) + ": the \"shared\" format stores H of blkdiag(H, H) once on one rank; its only "
-                                        "way of setting a matrix is cal_set_matrix_csr_stacked");
+                                        "ways of setting a matrix are cal_set_matrix_csr_stacked and "
+                                        "cal_set_matrix_csr_hermitian");
 }
 
 // the launch description of the shared stacked SpMV (H's arrays, 2 n_half-row vectors)
@@ -815,15 +825,20 @@ static SpmvArgs shared_args(const DevMatrix& A, const double* x, double* y, int 
     a.im2 = 0.0;
     a.xcd = 1;
     a.mode = mode | (A.nit << 8);
-    // col + val of H against the 256 MB Infinity Cache
-    a.nt = (int64_t)12 * A.nnz > ((int64_t)256 << 20) ? 1 : 0;
+    // col + val (+ vim) of H against the 256 MB Infinity Cache
+    a.nt = (int64_t)(A.herm ? 20 : 12) * A.nnz > ((int64_t)256 << 20) ? 1 : 0;
     return a;
 }
 
-// algorithmic bytes of a shared SpMV: H's col / val / rowptr once, x and y of
-// both halves, and the previous power / Lanczos vector when there is one
+// the stored-once SpMV of the matrix: k_spmv_herm on E(H), k_spmv_shared on blkdiag(H, H)
+static hipError_t launch_stored_once(const DevMatrix& A, const SpmvArgs& a, hipStream_t st) {
+    return A.herm ? launch_spmv_herm(a, A.vim, A.n_half, st) : launch_spmv_shared(a, A.n_half, st);
+}
+
+// algorithmic bytes of a shared SpMV: H's col / val (/ vim) / rowptr once, x and
+// y of both halves, and the previous power / Lanczos vector when there is one
 static double shared_spmv_bytes(const DevMatrix& A, bool prev) {
-    return 12.0 * A.nnz + 4.0 * (A.n_half + 1) + 32.0 * A.n_half + (prev ? 16.0 * A.n_half : 0.0);
+    return (A.herm ? 20.0 : 12.0) * A.nnz + 4.0 * (A.n_half + 1) + 32.0 * A.n_half + (prev ? 16.0 * A.n_half : 0.0);
 }
 
 // ---- the stored diagonal as a device vector ---------------------------------
@@ -1173,7 +1188,7 @@ int spmv_dev(cal_ctx* c, const double* x, double* y, int mode, double shift, dou
         a.im2 = im2;
         c->stat_spmv_rows += c->A.n_local;
         const int t = timer_begin(c, 0, shared_spmv_bytes(c->A, mode == 2));
-        CAL_HIP(c, launch_spmv_shared(a, c->A.n_half, c->stream));
+        CAL_HIP(c, launch_stored_once(c->A, a, c->stream));
         timer_end(c, t);
         return 0;
     }
@@ -1253,7 +1268,7 @@ int spmv_lanczos_dev(cal_ctx* c, const double* x, const double* xprev, const dou
         a.pb2 = has ? pb2 : nullptr;
         a.dotp = dotp;
         const int t = timer_begin(c, 0, shared_spmv_bytes(A, has));
-        CAL_HIP(c, launch_spmv_shared(a, A.n_half, c->stream));
+        CAL_HIP(c, launch_stored_once(A, a, c->stream));
         timer_end(c, t);
         return 0;
     }
@@ -1708,6 +1723,16 @@ int cal_spmv_split_info(cal_ctx* c, int* on, int64_t* P, int* H, int* neg1) {
     if (P) *P = s ? c->A.ds_P : 0;
     if (H) *H = s ? c->A.ds_H : 0;
     if (neg1) *neg1 = s && c->A.ds_neg1 ? 1 : 0;
+    return 0;
+}
+
+int cal_spmv_hermitian_info(cal_ctx* c, int* on, int64_t* n, int64_t* nnz_stored) {
+    if (!c) return CAL_ERR_ARG;
+    if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
+    const bool h = c->A.herm;
+    if (on) *on = h ? 1 : 0;
+    if (n) *n = h ? c->A.n_half : 0;
+    if (nnz_stored) *nnz_stored = h ? c->A.nnz : 0;
     return 0;
 }
 

@@ -94,6 +94,69 @@ def grid_hamiltonian(dims, V, h: float = 1.0, mass: float = 1.0) -> sp.csr_matri
     return sp.csr_matrix((val, col, rowptr), shape=(n, n))
 
 
+def peierls_hamiltonian(dims, V, flux: float, h: float = 1.0, mass: float = 1.0) -> sp.csr_matrix:
+    """``grid_hamiltonian(dims, V, h, mass)`` for a charged particle in a
+    uniform magnetic field along the last axis (2-D: out of the plane), in
+    Landau gauge: complex Hermitian CSR in the same row and column order.
+    ``flux`` is the flux through one plaquette of axes 0 and 1 in units of the
+    flux quantum.  The hops along axis 1 carry the Peierls phase: with t =
+    1/(2 m h^2), x0 the row's coordinate along axis 0 (the fastest) and s1 =
+    dims[0] the stride of axis 1,
+        H[r, r + s1] = -t exp(-2 pi i flux x0),  H[r, r - s1] = -t exp(+2 pi i flux x0);
+    every other entry is grid_hamiltonian's.  The matrix is Hermitian to the
+    bit (one cos and one sin per x0, the conjugate by negation), its diagonal
+    is real, and ``flux = 0`` gives grid_hamiltonian's values with an
+    imaginary part of explicit zeros."""
+    dims = tuple(int(d) for d in dims)
+    H = grid_hamiltonian(dims, V, h, mass)
+    n = H.shape[0]
+    re, col, rowptr = H.data, H.indices, H.indptr
+    im = np.zeros_like(re)
+    if dims[1] > 1:
+        s1 = dims[0]
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rowptr))
+        off = col.astype(np.int64) - rows
+        theta = 2.0 * np.pi * float(flux) * np.arange(dims[0], dtype=np.float64)
+        c, s = np.cos(theta)[rows % s1], np.sin(theta)[rows % s1]
+        up, dn = off == s1, off == -s1
+        ts = re * s  # (-t) sin(theta) on the hops
+        im[dn] = ts[dn] + 0.0  # -t (cos + i sin); + 0.0: never -0.0
+        im[up] = -ts[up] + 0.0  # -t (cos - i sin)
+        hop = up | dn
+        re[hop] = (re * c)[hop]
+    data = np.empty(re.shape[0], dtype=np.complex128)
+    data.real, data.imag = re, im
+    return sp.csr_matrix((data, col, rowptr), shape=(n, n))
+
+
+def hermitian_embedding(H) -> sp.csr_matrix:
+    """The real symmetric 2n x 2n matrix ``E(H) = [[A, -B], [B, A]]`` of a
+    Hermitian ``H = A + iB``: ``E(H) @ [Re psi; Im psi] = [Re(H psi); Im(H
+    psi)]``.  Row order of cal_set_matrix_csr_hermitian's host-built embedding:
+    top row i lists H's row i as (c, a) in stored order, then (n + c, -b);
+    bottom row n + i lists (c, b), then (n + c, a).  Explicit zeros are kept,
+    so the pattern does not depend on the values."""
+    H = to_csr(H)
+    if H.shape[0] != H.shape[1]:
+        raise ValueError("H must be square")
+    n, nnz = H.shape[0], H.nnz
+    rp =np.asarray(H.indptr, dtype=np.int64)
+    a = np.ascontiguousarray(H.data.real, dtype=np.float64)
+    b = np.ascontiguousarray(H.data.imag, dtype=np.float64) if np.iscomplexobj(H.data) else np.zeros(nnz)
+    cH = np.asarray(H.indices, dtype=np.int64)
+    p = np.arange(nnz, dtype=np.int64)
+    lo = np.repeat(rp[:-1], np.diff(rp)) + p  # 2 rowptr[i] + j: the row's first run
+    hi = np.repeat(rp[1:], np.diff(rp)) + p   # the second run, k entries on
+    col = np.empty(4 * nnz, dtype=np.int32)
+    val = np.empty(4 * nnz, dtype=np.float64)
+    col[lo], val[lo] = cH, a
+    col[hi], val[hi] = cH + n, -b
+    col[2 * nnz + lo], val[2 * nnz + lo] = cH, b
+    col[2 * nnz + hi], val[2 * nnz + hi] = cH + n, a
+    rowptr = np.concatenate([2 * rp, 2 * nnz + 2 * rp[1:]])
+    return sp.csr_matrix((val, col, rowptr), shape=(2 * n, 2 * n))
+
+
 def absorber_mask(dims, width: int, power: float = 0.125) -> np.ndarray:
     """The absorbing mask of ``Propagator.set_absorber`` on the grid ``dims``:
     the product over the axes of ``cos(pi/2 * r)**power`` (Krause, Schafer,

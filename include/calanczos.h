@@ -84,6 +84,44 @@ int cal_set_matrix_csr(cal_ctx* ctx, int64_t n, const int64_t* rowptr, const int
  * logical matrix, 2n rows and 2 nnz(H); cal_spmv_shared_info what is stored. */
 int cal_set_matrix_csr_stacked(cal_ctx* ctx, int64_t n, const int64_t* rowptr, const int32_t* colind,
                                const double* val);
+/* A complex Hermitian n x n CSR matrix H = A + iB (val_re, val_im; A real
+ * symmetric, B real antisymmetric) as the real symmetric 2n x 2n matrix
+ *     E(H) = [[A, -B], [B, A]]
+ * on the same stacked vectors: E(H) [Re psi; Im psi] = [Re H psi; Im H psi],
+ * so the time propagator (cal_prop_begin(ctx, n, ...)) and everything else that
+ * takes cal_set_matrix_csr_stacked's matrix take this one (magnetic fields,
+ * velocity gauge, rotating frames).  val_im == NULL is
+ * cal_set_matrix_csr_stacked(ctx, n, rowptr, colind, val_re): same code, same
+ * bits.  An all-zero val_im is not detected.
+ * The imaginary part of every stored diagonal entry must be exactly 0
+ * (CAL_ERR_ARG otherwise).  Hermiticity of the off-diagonal entries -- entry
+ * (j, i) stored as the conjugate of entry (i, j) -- is the caller's contract
+ * and is not checked, as symmetry is not for cal_set_matrix_csr.  Row pointers
+ * and column indices are checked as cal_set_matrix_csr_stacked checks them.
+ * With the "shared" format selected H is stored once: rowptr / col / val_re as
+ * for blkdiag(H, H) plus one array of nnz(H) imaginary parts, 20 bytes per
+ * nonzero of H (2n < 2^31, nnz(H) < 2^31, one rank).  Its SpMV forms, per stored
+ * nonzero (a, b) with x0 = x[c], x1 = x[n + c], the top half's term
+ * a*x0 - b*x1 and the bottom half's b*x0 + a*x1 (each product and the
+ * difference / sum rounded separately) and sums each row's terms in stored
+ * order from +0.0.  Such a matrix is a "shared" matrix in every other respect:
+ * cal_spmv_shared_info, cal_set_diagonal / cal_get_diagonal (the real diagonal;
+ * d[i] == d[n + i]) and the same CAL_ERR_UNSUPPORTED for normest, the Ritz
+ * residuals and the restart drivers; cal_matrix_info reports 2n rows and
+ * 4 nnz(H).
+ * With any other format E(H) is built on the host and handed to
+ * cal_set_matrix_csr (4 nnz(H) < 2^31): top row i lists H's row i as (c, a) in
+ * stored order, then (n + c, -b) in stored order; bottom row n + i lists
+ * (c, b), then (n + c, a); zeros are kept, so the pattern does not depend on
+ * the values.  That matrix runs everything the library has.
+ * Every eigenvalue of E(H) is double ([u; v] and [-v; u]): see DESIGN.md §4b
+ * before running a long eigen-solve on it. */
+int cal_set_matrix_csr_hermitian(cal_ctx* ctx, int64_t n, const int64_t* rowptr, const int32_t* colind,
+                                 const double* val_re, const double* val_im);
+/* *on = 1 when the resident matrix is a Hermitian H stored once (the "shared"
+ * format with a non-NULL val_im), with H's row count and stored nonzeros;
+ * zeros otherwise (the host-built embedding included). */
+int cal_spmv_hermitian_info(cal_ctx* ctx, int* on, int64_t* n, int64_t* nnz_stored);
 /* Row-slab of a distributed matrix: rows [row0, row0+nlocal) of the global
  * n_global x n_global matrix, global column indices.  Requires a communicator
  * (cal_comm_*) when nranks > 1. */
@@ -147,7 +185,8 @@ int cal_powers_launches(cal_ctx* ctx, int* launches);
  * the fused Lanczos step) loads every col / val entry once and applies it to
  * both halves, each row summed in the stacked CSR kernel's order -- y is
  * bit-identical to the stacked "csr" context.  With it selected every other
- * cal_set_matrix_* and a communicator of several ranks return
+ * cal_set_matrix_* but cal_set_matrix_csr_hermitian (which stores a complex
+ * Hermitian H once in the same way) and a communicator of several ranks return
  * CAL_ERR_UNSUPPORTED (the message names cal_set_matrix_csr_stacked); it never
  * falls back to another storage.  On a shared matrix whatever reads the CSR
  * rows of the whole matrix returns CAL_ERR_UNSUPPORTED and names "csr" as the

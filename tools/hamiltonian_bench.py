@@ -18,6 +18,13 @@ each in a fresh child process, alternating, --rounds times each:
          H stored once -- every leg (spmv, lanczos, prop; no ca) on the 2n rows
   csr2   Context(spmv_format="csr").set_matrix_stacked(H): the stacked CSR
          matrix, shared's A/B partner, same legs on the same 2n rows
+  herm   Context(spmv_format="shared").set_matrix_hermitian(H) with H =
+         peierls_hamiltonian on N^3 (the same potential, flux 1/16 per
+         plaquette): the complex Hermitian H stored once (k_spmv_herm), the
+         stacked legs on the 2n rows of [[A, -B], [B, A]]
+  herm_csr  the same H with spmv_format="csr": the host-built embedding on the
+         existing CSR kernel, herm's A/B partner ("herm_vs_herm_csr"; "herm_vs_shared"
+         holds herm against the real shared leg)
 A child measures, in --windows (>= 5) windows each after a warm-up:
   spmv     mode 0 back to back, 50 launches per window, each bracketed by the
            library's device events (cal_bench_spmv): mean us per launch;
@@ -70,7 +77,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 S, BLOCKS = 8, 3
-STACKED = ("shared", "csr2")  # variants whose spmv / lanczos legs run on blkdiag(H, H)
+HERM = ("herm", "herm_csr")  # the complex Hermitian H (set_matrix_hermitian)
+STACKED = ("shared", "csr2") + HERM  # variants whose spmv / lanczos legs run on the stacked 2n rows
+FLUX = 1.0 / 16.0
 SPMV_PER_WINDOW, CA_PER_WINDOW, LZ_PER_WINDOW, PROP_PER_WINDOW = 50, 10, 100, 4
 G_NL = 0.05  # the --nonlinear legs' coupling
 
@@ -83,6 +92,8 @@ def build(cal, np, variant, N):
     for d in range(3):
         x = (idx // N ** d) % N - 0.5 * (N - 1)
         r2 += x * x
+    if variant in HERM:
+        return cal.matrices.peierls_hamiltonian((N, N, N), 0.5 * 0.02 ** 2 * r2, FLUX)
     return cal.matrices.grid_hamiltonian((N, N, N), 0.5 * 0.02 ** 2 * r2)
 
 
@@ -97,10 +108,14 @@ def child(a):
     N, W = a.N, a.windows
     A = build(cal, np, a.variant, N)
     n = A.shape[0]
-    fmt = {"split": "split", "csr": "csr", "lap": "auto", "shared": "shared", "csr2": "csr"}[a.variant]
+    fmt = {"split": "split", "csr": "csr", "lap": "auto", "shared": "shared", "csr2": "csr",
+           "herm": "shared", "herm_csr": "csr"}[a.variant]
     stacked = a.variant in STACKED
     ctx = cal.Context(spmv_format=fmt)
-    if stacked:
+    if a.variant in HERM:
+        ctx.set_matrix_hermitian(A)
+        n = 2 * n
+    elif stacked:
         ctx.set_matrix_stacked(A)
         n = 2 * n  # the legs below run on the stacked problem
     else:
@@ -110,6 +125,8 @@ def child(a):
                spmv_format=ctx.spmv_format(), plane_info=ctx.spmv_plane_info(), split_info=ctx.spmv_split_info())
     if hasattr(ctx, "spmv_shared_info"):
         out["shared_info"] = ctx.spmv_shared_info()
+    if hasattr(ctx, "spmv_hermitian_info"):
+        out["hermitian_info"] = ctx.spmv_hermitian_info()
     only = a.only.split(",")
     if "spmv" in only:
         ctx.bench_spmv(20)
@@ -301,7 +318,7 @@ def main():
     legs += [("%s+drive%s" % (v, d), v, d, None, "0") for v in variants if v != "lap" for d in drives if d != "0"]
     legs += [("%s+nl%s" % (v, x), v, "0", None, x) for v in variants if v != "lap" for x in nls]
     if a.package_root:
-        legs += [("%s@root" % v, v, "0", a.package_root, "0") for v in variants if v != "shared"]
+        legs += [("%s@root" % v, v, "0", a.package_root, "0") for v in variants if v != "shared" and v not in HERM]
     variants = [l[0] for l in legs]
     res = dict(N=a.N, n=a.N ** 3, rounds=a.rounds, windows=a.windows, only=a.only, library=a.library or "production",
                s=S, blocks=BLOCKS, runs={v: [] for v in variants})
@@ -336,6 +353,10 @@ def main():
                 b = 2.0 * (12.0 * nnz + 20.0 * n)
             if v == "shared":
                 b = 12.0 * nnz + 4.0 * (n + 1) + 32.0 * n
+            if v == "herm":
+                b = 20.0 * nnz + 4.0 * (n + 1) + 32.0 * n
+            if v == "herm_csr":  # the embedding's 4 nnz entries and 2n rows on the CSR kernel
+                b = 2.0 * (24.0 * nnz + 20.0 * n)
             summ[v]["spmv"]["algorithmic_TBps"] = b / (summ[v]["spmv"]["median"] * 1e-6) / 1e12
     if "split" in summ and "csr" in summ:
         res["split_vs_csr"] = {
@@ -343,8 +364,9 @@ def main():
                     beyond_spread=bool(summ["split"][k]["max"] < summ["csr"][k]["min"]))
             for k in summ["split"] if k in summ["csr"]}
     for name, other in (("shared_vs_csr2", "csr2"), ("shared_vs_parent", "csr2@root"),
-                        ("shared_vs_csr2_driven", "csr2+drive1")):
-        mine = "shared+drive1" if other.endswith("drive1") else "shared"
+                        ("shared_vs_csr2_driven", "csr2+drive1"), ("herm_vs_herm_csr", "herm_csr"),
+                        ("herm_vs_shared", "shared")):
+        mine = "shared+drive1" if other.endswith("drive1") else "herm" if name.startswith("herm") else "shared"
         if mine in summ and other in summ:
             res[name] = {
                 k: dict(ratio=summ[other][k]["median"] / summ[mine][k]["median"],
