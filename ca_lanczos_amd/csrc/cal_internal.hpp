@@ -185,6 +185,10 @@ struct DevMatrix {
     int nit = 1;     // ceil(max row-block nonzeros / 256): SpMV unroll depth
     int64_t ld = 0;  // leading dimension of every n-vector buffer
     int64_t lpad = 0;  // offset of the local origin inside each vector column
+    // The storage flags below (use_pat, use_dsplit, shared, herm) are set at the
+    // upload and obey: herm => shared; shared => !use_pat && !use_dsplit;
+    // use_dsplit => !use_pat.  None set: plain CSR.  The SpMV dispatch turns
+    // them into one storage choice (runtime.cpp spmv_store).
     // row-pattern format (chosen automatically when the table is small)
     bool use_pat = false;
     uint16_t* pat = nullptr;
@@ -274,13 +278,12 @@ struct StdLanczosState;  // lanczos_std.cpp
 
 // Launchers (kernels.hip).  All enqueue on `st` and return hipError_t.
 hipError_t launch_spmv(const SpmvArgs& a, hipStream_t st);
-// the shared stacked SpMV (k_spmv_shared): a holds H's CSR arrays and row
+// the stored-once stacked SpMV (k_spmv_stacked): a holds H's CSR arrays and row
 // blocks, the vectors have 2 n_half rows; modes 0, 1, 2 and 4 (mode 4 writes
-// 2 a.nblk partials: the top half's, then the bottom half's)
-hipError_t launch_spmv_shared(const SpmvArgs& a, int64_t n_half, hipStream_t st);
-// the Hermitian stored-once SpMV (k_spmv_herm): as launch_spmv_shared, with
-// a.val the real parts and vim the imaginary parts of H's nonzeros
-hipError_t launch_spmv_herm(const SpmvArgs& a, const double* vim, int64_t n_half, hipStream_t st);
+// 2 a.nblk partials: the top half's, then the bottom half's).  vim null: the
+// shared format, blkdiag(H, H) of the real H in a.val; otherwise the Hermitian
+// one, E(H) with a.val the real and vim the imaginary parts of H's nonzeros
+hipError_t launch_spmv_stacked(const SpmvArgs& a, const double* vim, int64_t n_half, hipStream_t st);
 hipError_t launch_spmv_pat(const PatArgs& a, hipStream_t st);
 // mode 4's grid = its number of y'x partials (0: this storage has no fused
 // Lanczos mode -- the row-pattern kernels k_spmv_pat / k_spmv_pat_lds)

@@ -12,11 +12,11 @@
 //                   MODE 4 (here, in k_spmv_pair and in k_spmv_planes): the
 //                   standard Lanczos step y = A x - beta xprev with the block
 //                   partials of y'x (lanczos.m:103-107; lz_sub, lz_block_sum).
-//   k_spmv_shared   the same on blkdiag(H, H) with H stored once: one load of
-//                   col / val, two gathers, two products, both halves' rows.
-//   k_spmv_herm     the same on [[A, -B], [B, A]] for a complex Hermitian
-//                   H = A + iB stored once: one more value per nonzero, the
-//                   two gathers cross-mixed.
+//   k_spmv_stacked  the same on a stacked matrix with H stored once: one load
+//                   of col / val, two gathers, both halves' rows.  HERM false:
+//                   blkdiag(H, H), two products; HERM true: [[A, -B], [B, A]]
+//                   for a complex Hermitian H = A + iB, one more value per
+//                   nonzero, the two gathers cross-mixed.
 //   k_spmv_pat_lds, k_spmv_pair
 //                   row-pattern SpMV (lossless pattern table, one / two rows
 //                   per lane), same arithmetic, same shift epilogue; the pair
@@ -233,25 +233,33 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv(SpmvArgs a) {
     }
 }
 
+// the per-matrix iteration count nit (1..8; anything else takes 8) as a
+// compile-time NIT: f(std::integral_constant<int, NIT>)
+template <typename F>
+static void nit_dispatch(int nit, F&& f) {
+    switch (nit) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 7: f(std::integral_constant<int, 7>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+
 template <int MODE, bool NT, int V>
 static hipError_t launch_spmv_mode2(const SpmvArgs& a, int nit, hipStream_t st) {
-    dim3 g(a.nblk), b(kSpmvThreads);
-    switch (nit) {
-        case 1: hipLaunchKernelGGL((k_spmv<MODE, 1, NT, V>), g, b, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_spmv<MODE, 2, NT, V>), g, b, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((k_spmv<MODE, 3, NT, V>), g, b, 0, st, a); break;
-        case 4: hipLaunchKernelGGL((k_spmv<MODE, 4, NT, V>), g, b, 0, st, a); break;
-        case 5: hipLaunchKernelGGL((k_spmv<MODE, 5, NT, V>), g, b, 0, st, a); break;
-        case 6: hipLaunchKernelGGL((k_spmv<MODE, 6, NT, V>), g, b, 0, st, a); break;
-        case 7: hipLaunchKernelGGL((k_spmv<MODE, 7, NT, V>), g, b, 0, st, a); break;
-        default: hipLaunchKernelGGL((k_spmv<MODE, 8, NT, V>), g, b, 0, st, a); break;
-    }
+    nit_dispatch(nit, [&](auto n) {
+        hipLaunchKernelGGL((k_spmv<MODE, decltype(n)::value, NT, V>), dim3(a.nblk), dim3(kSpmvThreads), 0, st, a);
+    });
     return hipGetLastError();
 }
 
 // one nonzero per thread and iteration (two: slower on both matrices below).
 // col / val stream once per SpMV: when the matrix is larger than the
-// Infinity Cache (a.nt, set by spmv_dev) they are loaded non-temporally, so
+// Infinity Cache (a.nt, runtime.cpp spmv_nt) they are loaded non-temporally, so
 // the cache keeps x's lines for the neighbouring rows' gathers -- 200 vs
 // 208 us on lap3d_215 in CSR (1.03 GB); a matrix that fits (circuit_1259,
 // 123 MB) is still there at the next SpMV and keeps plain loads (23.0 us,
@@ -280,16 +288,25 @@ hipError_t launch_spmv(const SpmvArgs& a0, hipStream_t st) {
 }
 
 // --------------------------------------------------------------------------
-// The shared stacked SpMV ("shared"): y = blkdiag(H, H) x on the
-// stacked vectors [Re; Im] of 2 nh rows with H stored once.  The grid, the row
-// blocks and the load phase are k_spmv's over H's nh rows; every nonzero is
-// loaded once, gathers x[c] and x[nh + c], and its two products go to LDS.
-// Thread <-> row as in k_spmv, so each half's row sums -- and MODE 4's block
-// partials, dotp[b] for the top half and dotp[nblk + b] for the bottom one --
-// are the bits k_spmv gives on the stacked matrix (whose row blocks then do
-// not straddle row nh).  MODE 3 (normest) is not built.
+// The stored-once stacked SpMV ("shared" and the Hermitian
+// format): y = M x on the stacked vectors [Re; Im] of 2 nh rows with H stored
+// once.  The grid, the row blocks and the load phase are k_spmv's over H's nh
+// rows; every nonzero is loaded once, gathers x0 = x[c] and x1 = x[nh + c], and
+// its two terms -- the top half's and the bottom half's -- go to LDS:
+//     HERM false  M = blkdiag(H, H), H real (a.val; vim never touched):
+//                     v*x0                  v*x1
+//     HERM true   M = E(H) = [[A, -B], [B, A]] for the complex Hermitian
+//                 H = A + iB (a.val = A's values, vim = B's, one col / rowptr):
+//                     a*x0 - b*x1           b*x0 + a*x1
+// with every product and the difference / sum rounded on its own (the file is
+// built -ffp-contract=off; herm_term spells the temporaries out).  Each row sums
+// its terms in stored order from +0.0 (tests/herm_ref.py herm_chain restates
+// it).  Thread <-> row as in k_spmv, so each half's row sums -- and MODE 4's
+// block partials, dotp[b] for the top half and dotp[nblk + b] for the bottom
+// one -- are the bits k_spmv gives on the stacked matrix (whose row blocks then
+// do not straddle row nh).  MODE 3 (normest) is not built.
 //
-// The two products of a nonzero are one 16-B LDS element (one ds_write_b128,
+// The two terms of a nonzero are one 16-B LDS element (one ds_write_b128,
 // one ds_read_b128 per j of the row sum); CAL_SHARED_LDS_SPLIT = 1 keeps them
 // in two 8-B arrays instead (the A/B of DESIGN.md §3; 32 KiB either way).
 #ifndef CAL_SHARED_LDS_SPLIT
@@ -322,9 +339,16 @@ struct SharedProd {
 #endif
 };
 
-template <int MODE, int NIT, bool NT>
-__global__ __launch_bounds__(kSpmvThreads) void k_spmv_shared(SpmvArgs a, int nh) {
-    static_assert(MODE == 0 || MODE == 1 || MODE == 2 || MODE == 4, "k_spmv_shared: modes 0, 1, 2 and 4");
+__device__ __forceinline__ void herm_term(double a, double b, double x0, double x1, double& pt, double& pb) {
+    const double t0 = a * x0, t1 = b * x1;
+    const double u0 = b * x0, u1 = a * x1;
+    pt = t0 - t1;
+    pb = u0 + u1;
+}
+
+template <int MODE, int NIT, bool NT, bool HERM>
+__global__ __launch_bounds__(kSpmvThreads) void k_spmv_stacked(SpmvArgs a, const double* vim, int nh) {
+    static_assert(MODE == 0 || MODE == 1 || MODE == 2 || MODE == 4, "k_spmv_stacked: modes 0, 1, 2 and 4");
     __shared__ SharedProd prod;
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int tid = threadIdx.x;
@@ -336,18 +360,33 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv_shared(SpmvArgs a, int nh
     const double lzb = lzhas ? sqrt(*a.pb2) : 0.0;
     const double* lzq = lzhas ? a.xprev : a.x;
     double lzd0 = 0.0, lzd1 = 0.0;  // MODE 4: the thread's y * x, per half
+    // one row's two sums -> y of both halves (and MODE 4's y * x)
+    auto finish = [&](int r, double s0, double s1) {
+        if (MODE == 4) {
+            const double y0 = lz_sub(s0, lzb, lzq[r], lzhas);
+            const double y1 = lz_sub(s1, lzb, lzq[nh + r], lzhas);
+            a.y[r] = y0;
+            a.y[nh + r] = y1;
+            lzd0 = y0 * a.x[r];
+            lzd1 = y1 * xb[r];
+        } else {
+            a.y[r] = spmv_epilogue<MODE>(s0, a, r);
+            a.y[nh + r] = spmv_epilogue<MODE>(s1, a, nh + r);
+        }
+    };
     if (cnt <= kSpmvNnz) {
         if (cnt > 0) {
-            // k_spmv's phases: all col / val loads (clamped, unbranched), then
-            // both gathers of every nonzero, then the LDS products
+            // k_spmv's phases: all col / val (/ vim) loads (clamped, unbranched),
+            // then both gathers of every nonzero, then the LDS terms
             const int pl = p1 - 1;
             int ci[NIT];
-            double v[NIT], x0[NIT], x1[NIT];
+            double v[NIT], vi[HERM ? NIT : 1], x0[NIT], x1[NIT];
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const int p = min(p0 + it * kSpmvThreads + tid, pl);
                 ci[it] = ldnt<NT>(a.col + p);
                 v[it] = ldnt<NT>(a.val + p);
+                if constexpr (HERM) vi[it] = ldnt<NT>(vim + p);
             }
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
@@ -357,7 +396,13 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv_shared(SpmvArgs a, int nh
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const int q = it * kSpmvThreads + tid;
-                if (q < cnt) prod.put(q, v[it] * x0[it], v[it] * x1[it]);
+                if constexpr (HERM) {
+                    double pt, pb;
+                    herm_term(v[it], vi[it], x0[it], x1[it], pt, pb);
+                    if (q < cnt) prod.put(q, pt, pb);
+                } else {
+                    if (q < cnt) prod.put(q, v[it] * x0[it], v[it] * x1[it]);
+                }
             }
         }
         __syncthreads();
@@ -366,17 +411,7 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv_shared(SpmvArgs a, int nh
             const int q0 = a.rowptr[r] - p0, q1 = a.rowptr[r + 1] - p0;
             double s0 = 0.0, s1 = 0.0;
             for (int j = q0; j < q1; ++j) prod.add(j, s0, s1);
-            if (MODE == 4) {
-                const double y0 = lz_sub(s0, lzb, lzq[r], lzhas);
-                const double y1 = lz_sub(s1, lzb, lzq[nh + r], lzhas);
-                a.y[r] = y0;
-                a.y[nh + r] = y1;
-                lzd0 = y0 * a.x[r];
-                lzd1 = y1 * xb[r];
-            } else {
-                a.y[r] = spmv_epilogue<MODE>(s0, a, r);
-                a.y[nh + r] = spmv_epilogue<MODE>(s1, a, nh + r);
-            }
+            finish(r, s0, s1);
         }
     } else {
         // one long row (> kSpmvNnz nonzeros): chunked, both sums still in order
@@ -386,26 +421,20 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv_shared(SpmvArgs a, int nh
             for (int q = tid; q < m; q += kSpmvThreads) {
                 const int cc = a.col[c + q];
                 const double vq = a.val[c + q];
-                prod.put(q, vq * a.x[cc], vq * xb[cc]);
+                if constexpr (HERM) {
+                    double pt, pb;
+                    herm_term(vq, vim[c + q], a.x[cc], xb[cc], pt, pb);
+                    prod.put(q, pt, pb);
+                } else {
+                    prod.put(q, vq * a.x[cc], vq * xb[cc]);
+                }
             }
             __syncthreads();
             if (tid == 0)
                 for (int j = 0; j < m; ++j) prod.add(j, s0, s1);
             __syncthreads();
         }
-        if (tid == 0) {  // the one thread that holds the row's sums
-            if (MODE == 4) {
-                const double y0 = lz_sub(s0, lzb, lzq[r0], lzhas);
-                const double y1 = lz_sub(s1, lzb, lzq[nh + r0], lzhas);
-                a.y[r0] = y0;
-                a.y[nh + r0] = y1;
-                lzd0 = y0 * a.x[r0];
-                lzd1 = y1 * xb[r0];
-            } else {
-                a.y[r0] = spmv_epilogue<MODE>(s0, a, r0);
-                a.y[nh + r0] = spmv_epilogue<MODE>(s1, a, nh + r0);
-            }
-        }
+        if (tid == 0) finish(r0, s0, s1);  // the one thread that holds the row's sums
     }
     if constexpr (MODE == 4) {
         // the wave sums reuse the products' LDS once every row is summed: 32 KiB
@@ -421,197 +450,38 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv_shared(SpmvArgs a, int nh
     }
 }
 
-template <int MODE, bool NT>
-static hipError_t launch_spmv_shared_nit(const SpmvArgs& a, int nh, int nit, hipStream_t st) {
-    dim3 g(a.nblk), b(kSpmvThreads);
-    switch (nit) {
-        case 1: hipLaunchKernelGGL((k_spmv_shared<MODE, 1, NT>), g, b, 0, st, a, nh); break;
-        case 2: hipLaunchKernelGGL((k_spmv_shared<MODE, 2, NT>), g, b, 0, st, a, nh); break;
-        case 3: hipLaunchKernelGGL((k_spmv_shared<MODE, 3, NT>), g, b, 0, st, a, nh); break;
-        case 4: hipLaunchKernelGGL((k_spmv_shared<MODE, 4, NT>), g, b, 0, st, a, nh); break;
-        case 5: hipLaunchKernelGGL((k_spmv_shared<MODE, 5, NT>), g, b, 0, st, a, nh); break;
-        case 6: hipLaunchKernelGGL((k_spmv_shared<MODE, 6, NT>), g, b, 0, st, a, nh); break;
-        case 7: hipLaunchKernelGGL((k_spmv_shared<MODE, 7, NT>), g, b, 0, st, a, nh); break;
-        default: hipLaunchKernelGGL((k_spmv_shared<MODE, 8, NT>), g, b, 0, st, a, nh); break;
-    }
-    return hipGetLastError();
-}
-
 template <int MODE>
-static hipError_t launch_spmv_shared_mode(const SpmvArgs& a, int nh, int nit, hipStream_t st) {
-    return a.nt ? launch_spmv_shared_nit<MODE, true>(a, nh, nit, st) : launch_spmv_shared_nit<MODE, false>(a, nh, nit, st);
+static hipError_t launch_spmv_stacked_mode(const SpmvArgs& a, const double* vim, int nh, hipStream_t st) {
+    nit_dispatch((a.mode >> 8) & 0xff, [&](auto n) {
+        constexpr int NIT = decltype(n)::value;
+        auto go = [&](auto nt, auto herm) {
+            hipLaunchKernelGGL((k_spmv_stacked<MODE, NIT, decltype(nt)::value, decltype(herm)::value>), dim3(a.nblk),
+                               dim3(kSpmvThreads), 0, st, a, vim, nh);
+        };
+        using T = std::true_type;
+        using N = std::false_type;
+        if (vim) a.nt ? go(T{}, T{}) : go(N{}, T{});
+        else a.nt ? go(T{}, N{}) : go(N{}, N{});
+    });
+    return hipGetLastError();
 }
 
 // a: H's CSR arrays and row blocks (a.nblk of them), x / y / xprev the stacked
-// vectors of 2 n_half rows, mode | nit << 8 as for launch_spmv
-hipError_t launch_spmv_shared(const SpmvArgs& a, int64_t n_half, hipStream_t st) {
+// vectors of 2 n_half rows, mode | nit << 8 as for launch_spmv.  vim: the
+// imaginary parts of H's nonzeros in a.val's order (HERM), null for a real H
+hipError_t launch_spmv_stacked(const SpmvArgs& a, const double* vim, int64_t n_half, hipStream_t st) {
     if (a.nblk <= 0) return hipSuccess;
     if (n_half < 1 || 2 * n_half >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    const int nit = (a.mode >> 8) & 0xff, nh = (int)n_half;
+    const int nh = (int)n_half;
     switch (a.mode & 0xff) {
-        case 0: return launch_spmv_shared_mode<0>(a, nh, nit, st);
-        case 1: return launch_spmv_shared_mode<1>(a, nh, nit, st);
-        case 2: return a.xprev ? launch_spmv_shared_mode<2>(a, nh, nit, st) : hipErrorInvalidValue;
-        case 4: return a.dotp ? launch_spmv_shared_mode<4>(a, nh, nit, st) : hipErrorInvalidValue;
+        case 0: return launch_spmv_stacked_mode<0>(a, vim, nh, st);
+        case 1: return launch_spmv_stacked_mode<1>(a, vim, nh, st);
+        case 2: return a.xprev ? launch_spmv_stacked_mode<2>(a, vim, nh, st) : hipErrorInvalidValue;
+        case 4: return a.dotp ? launch_spmv_stacked_mode<4>(a, vim, nh, st) : hipErrorInvalidValue;
         default: return hipErrorInvalidValue;
     }
 }
 
-// --------------------------------------------------------------------------
-// The Hermitian stored-once SpMV: y = E(H) x with E(H) =
-// [[A, -B], [B, A]] for the complex Hermitian H = A + iB, H stored once (a.val
-// = A's values, vim = B's, one col / rowptr).  Grid, row blocks, thread <-> row,
-// the epilogues and MODE 4's partial layout are k_spmv_shared's; a nonzero
-// loads one more value and cross-mixes its two gathers x0 = x[c], x1 = x[nh + c]:
-//     top half's term     a*x0 - b*x1
-//     bottom half's term  b*x0 + a*x1
-// with every product and the difference / sum rounded on its own (the file is
-// built -ffp-contract=off; herm_term spells the temporaries out).  Each row sums
-// its terms in stored order from +0.0 (tests/herm_ref.py herm_chain restates it).
-__device__ __forceinline__ void herm_term(double a, double b, double x0, double x1, double& pt, double& pb) {
-    const double t0 = a * x0, t1 = b * x1;
-    const double u0 = b * x0, u1 = a * x1;
-    pt = t0 - t1;
-    pb = u0 + u1;
-}
-
-template <int MODE, int NIT, bool NT>
-__global__ __launch_bounds__(kSpmvThreads) void k_spmv_herm(SpmvArgs a, const double* vim, int nh) {
-    static_assert(MODE == 0 || MODE == 1 || MODE == 2 || MODE == 4, "k_spmv_herm: modes 0, 1, 2 and 4");
-    __shared__ SharedProd prod;
-    const int b = xcd_remap(blockIdx.x, gridDim.x);
-    const int tid = threadIdx.x;
-    const int r0 = a.blk[b], r1 = a.blk[b + 1];
-    const int p0 = a.rowptr[r0], p1 = a.rowptr[r1];
-    const int cnt = p1 - p0;
-    const double* xb = a.x + nh;  // the bottom half
-    const bool lzhas = MODE == 4 && a.xprev && a.pb2;
-    const double lzb = lzhas ? sqrt(*a.pb2) : 0.0;
-    const double* lzq = lzhas ? a.xprev : a.x;
-    double lzd0 = 0.0, lzd1 = 0.0;  // MODE 4: the thread's y * x, per half
-    if (cnt <= kSpmvNnz) {
-        if (cnt > 0) {
-            // all col / val / vim loads (clamped, unbranched), then both gathers
-            // of every nonzero, then the LDS terms
-            const int pl = p1 - 1;
-            int ci[NIT];
-            double vr[NIT], vi[NIT], x0[NIT], x1[NIT];
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int p = min(p0 + it * kSpmvThreads + tid, pl);
-                ci[it] = ldnt<NT>(a.col + p);
-                vr[it] = ldnt<NT>(a.val + p);
-                vi[it] = ldnt<NT>(vim + p);
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                x0[it] = a.x[ci[it]];
-                x1[it] = xb[ci[it]];
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int q = it * kSpmvThreads + tid;
-                double pt, pb;
-                herm_term(vr[it], vi[it], x0[it], x1[it], pt, pb);
-                if (q < cnt) prod.put(q, pt, pb);
-            }
-        }
-        __syncthreads();
-        const int r = r0 + tid;
-        if (r < r1) {
-            const int q0 = a.rowptr[r] - p0, q1 = a.rowptr[r + 1] - p0;
-            double s0 = 0.0, s1 = 0.0;
-            for (int j = q0; j < q1; ++j) prod.add(j, s0, s1);
-            if (MODE == 4) {
-                const double y0 = lz_sub(s0, lzb, lzq[r], lzhas);
-                const double y1 = lz_sub(s1, lzb, lzq[nh + r], lzhas);
-                a.y[r] = y0;
-                a.y[nh + r] = y1;
-                lzd0 = y0 * a.x[r];
-                lzd1 = y1 * xb[r];
-            } else {
-                a.y[r] = spmv_epilogue<MODE>(s0, a, r);
-                a.y[nh + r] = spmv_epilogue<MODE>(s1, a, nh + r);
-            }
-        }
-    } else {
-        // one long row (> kSpmvNnz nonzeros): chunked, both sums still in order
-        double s0 = 0.0, s1 = 0.0;
-        for (int c = p0; c < p1; c += kSpmvNnz) {
-            const int m = min(kSpmvNnz, p1 - c);
-            for (int q = tid; q < m; q += kSpmvThreads) {
-                const int cc = a.col[c + q];
-                double pt, pb;
-                herm_term(a.val[c + q], vim[c + q], a.x[cc], xb[cc], pt, pb);
-                prod.put(q, pt, pb);
-            }
-            __syncthreads();
-            if (tid == 0)
-                for (int j = 0; j < m; ++j) prod.add(j, s0, s1);
-            __syncthreads();
-        }
-        if (tid == 0) {  // the one thread that holds the row's sums
-            if (MODE == 4) {
-                const double y0 = lz_sub(s0, lzb, lzq[r0], lzhas);
-                const double y1 = lz_sub(s1, lzb, lzq[nh + r0], lzhas);
-                a.y[r0] = y0;
-                a.y[nh + r0] = y1;
-                lzd0 = y0 * a.x[r0];
-                lzd1 = y1 * xb[r0];
-            } else {
-                a.y[r0] = spmv_epilogue<MODE>(s0, a, r0);
-                a.y[nh + r0] = spmv_epilogue<MODE>(s1, a, nh + r0);
-            }
-        }
-    }
-    if constexpr (MODE == 4) {
-        // as k_spmv_shared: the wave sums reuse the products' LDS (32 KiB, five blocks per CU)
-        __syncthreads();
-        double* ws = reinterpret_cast<double*>(&prod);
-        const double t0 = lz_block_sum<kSpmvThreads / 64>(lzd0, ws);
-        const double t1 = lz_block_sum<kSpmvThreads / 64>(lzd1, ws + kSpmvThreads / 64);
-        if (tid == 0) {
-            a.dotp[b] = t0;
-            a.dotp[gridDim.x + b] = t1;
-        }
-    }
-}
-
-template <int MODE, bool NT>
-static hipError_t launch_spmv_herm_nit(const SpmvArgs& a, const double* vim, int nh, int nit, hipStream_t st) {
-    dim3 g(a.nblk), b(kSpmvThreads);
-    switch (nit) {
-        case 1: hipLaunchKernelGGL((k_spmv_herm<MODE, 1, NT>), g, b, 0, st, a, vim, nh); break;
-        case 2: hipLaunchKernelGGL((k_spmv_herm<MODE, 2, NT>), g, b, 0, st, a, vim, nh); break;
-        case 3: hipLaunchKernelGGL((k_spmv_herm<MODE, 3, NT>), g, b, 0, st, a, vim, nh); break;
-        case 4: hipLaunchKernelGGL((k_spmv_herm<MODE, 4, NT>), g, b, 0, st, a, vim, nh); break;
-        case 5: hipLaunchKernelGGL((k_spmv_herm<MODE, 5, NT>), g, b, 0, st, a, vim, nh); break;
-        case 6: hipLaunchKernelGGL((k_spmv_herm<MODE, 6, NT>), g, b, 0, st, a, vim, nh); break;
-        case 7: hipLaunchKernelGGL((k_spmv_herm<MODE, 7, NT>), g, b, 0, st, a, vim, nh); break;
-        default: hipLaunchKernelGGL((k_spmv_herm<MODE, 8, NT>), g, b, 0, st, a, vim, nh); break;
-    }
-    return hipGetLastError();
-}
-
-template <int MODE>
-static hipError_t launch_spmv_herm_mode(const SpmvArgs& a, const double* vim, int nh, int nit, hipStream_t st) {
-    return a.nt ? launch_spmv_herm_nit<MODE, true>(a, vim, nh, nit, st)
-                : launch_spmv_herm_nit<MODE, false>(a, vim, nh, nit, st);
-}
-
-// as launch_spmv_shared; vim: the imaginary parts of H's nonzeros, in a.val's order
-hipError_t launch_spmv_herm(const SpmvArgs& a, const double* vim, int64_t n_half, hipStream_t st) {
-    if (a.nblk <= 0) return hipSuccess;
-    if (!vim || n_half < 1 || 2 * n_half >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    const int nit = (a.mode >> 8) & 0xff, nh = (int)n_half;
-    switch (a.mode & 0xff) {
-        case 0: return launch_spmv_herm_mode<0>(a, vim, nh, nit, st);
-        case 1: return launch_spmv_herm_mode<1>(a, vim, nh, nit, st);
-        case 2: return a.xprev ? launch_spmv_herm_mode<2>(a, vim, nh, nit, st) : hipErrorInvalidValue;
-        case 4: return a.dotp ? launch_spmv_herm_mode<4>(a, vim, nh, nit, st) : hipErrorInvalidValue;
-        default: return hipErrorInvalidValue;
-    }
-}
 
 // --------------------------------------------------------------------------
 // Row-pattern SpMV (same arithmetic as k_spmv, different storage): thread

@@ -573,6 +573,26 @@ static bool split_analyze(int64_t n, const std::vector<int>& rowptr, const std::
     return true;
 }
 
+// The CSR arrays of c->A (n_rows stored rows, A.nnz entries) and its row
+// blocks (build_row_blocks' blk and max_nnz) on the device, with nblk and nit.
+static int upload_csr(cal_ctx* c, int64_t n_rows, const std::vector<int>& rowptr, const std::vector<int>& col,
+                      const double* val, const std::vector<int>& blk, int max_nnz) {
+    DevMatrix& A = c->A;
+    A.nblk = (int)blk.size() - 1;
+    A.nit = std::min(8, std::max(1, (max_nnz + 255) / 256));
+    CAL_HIP(c, hipMalloc((void**)&A.rowptr, (n_rows + 1) * sizeof(int)));
+    CAL_HIP(c, hipMalloc((void**)&A.col, std::max<int64_t>(A.nnz, 1) * sizeof(int)));
+    CAL_HIP(c, hipMalloc((void**)&A.val, std::max<int64_t>(A.nnz, 1) * sizeof(double)));
+    CAL_HIP(c, hipMalloc((void**)&A.blk, blk.size() * sizeof(int)));
+    CAL_HIP(c, hipMemcpy(A.rowptr, rowptr.data(), (n_rows + 1) * sizeof(int), hipMemcpyHostToDevice));
+    if (A.nnz > 0) {
+        CAL_HIP(c, hipMemcpy(A.col, col.data(), A.nnz * sizeof(int), hipMemcpyHostToDevice));
+        CAL_HIP(c, hipMemcpy(A.val, val, A.nnz * sizeof(double), hipMemcpyHostToDevice));
+    }
+    CAL_HIP(c, hipMemcpy(A.blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
+
 // Upload a local matrix: n_rows stored rows, the n_local local ones from
 // stored row ext_off.  col: local column ids relative to the local origin
 // (negative ids address the left halo); lpad / rext: halo extent on either
@@ -719,7 +739,6 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
     int max_nnz = 0;
     std::vector<int> rp_loc(rowptr.begin() + ext_off, rowptr.begin() + ext_off + n_local + 1);
     build_row_blocks(n_local, rp_loc, blk, &max_nnz);
-    A.nblk = (int)blk.size() - 1;
     // the split format's fused Lanczos dot sums in the CSR kernel's order, which
     // it takes to be 256 consecutive rows per block (rows of at most 8 entries)
     // -- a guard, not a case that occurs.  "auto" then goes on with CSR.
@@ -731,20 +750,7 @@ int upload_matrix(cal_ctx* c, int64_t n_rows, int64_t ext_off, int64_t n_local, 
                     return set_error(c, CAL_ERR_UNSUPPORTED, "diagonal-split format: unexpected CSR row blocks");
                 break;
             }
-    int nit = (max_nnz + 255) / 256;
-    if (nit < 1) nit = 1;
-    if (nit > 8) nit = 8;
-    A.nit = nit;
-    CAL_HIP(c, hipMalloc((void**)&A.rowptr, (n_rows + 1) * sizeof(int)));
-    CAL_HIP(c, hipMalloc((void**)&A.col, std::max<int64_t>(A.nnz, 1) * sizeof(int)));
-    CAL_HIP(c, hipMalloc((void**)&A.val, std::max<int64_t>(A.nnz, 1) * sizeof(double)));
-    CAL_HIP(c, hipMalloc((void**)&A.blk, blk.size() * sizeof(int)));
-    CAL_HIP(c, hipMemcpy(A.rowptr, rowptr.data(), (n_rows + 1) * sizeof(int), hipMemcpyHostToDevice));
-    if (A.nnz > 0) {
-        CAL_HIP(c, hipMemcpy(A.col, col.data(), A.nnz * sizeof(int), hipMemcpyHostToDevice));
-        CAL_HIP(c, hipMemcpy(A.val, val, A.nnz * sizeof(double), hipMemcpyHostToDevice));
-    }
-    CAL_HIP(c, hipMemcpy(A.blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
+    CAL_TRY(upload_csr(c, n_rows, rowptr, col, val, blk, max_nnz));
     c->has_A = true;
     c->A_gen++;
     return 0;
@@ -770,22 +776,11 @@ int upload_matrix_shared(cal_ctx* c, int64_t n, const std::vector<int>& rowptr, 
     std::vector<int> blk;
     int max_nnz = 0;
     build_row_blocks(n, rowptr, blk, &max_nnz);
-    A.nblk = (int)blk.size() - 1;
-    A.nit = std::min(8, std::max(1, (max_nnz + 255) / 256));
-    CAL_HIP(c, hipMalloc((void**)&A.rowptr, (n + 1) * sizeof(int)));
-    CAL_HIP(c, hipMalloc((void**)&A.col, std::max<int64_t>(A.nnz, 1) * sizeof(int)));
-    CAL_HIP(c, hipMalloc((void**)&A.val, std::max<int64_t>(A.nnz, 1) * sizeof(double)));
-    CAL_HIP(c, hipMalloc((void**)&A.blk, blk.size() * sizeof(int)));
-    CAL_HIP(c, hipMemcpy(A.rowptr, rowptr.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice));
-    if (A.nnz > 0) {
-        CAL_HIP(c, hipMemcpy(A.col, col.data(), A.nnz * sizeof(int), hipMemcpyHostToDevice));
-        CAL_HIP(c, hipMemcpy(A.val, val, A.nnz * sizeof(double), hipMemcpyHostToDevice));
-    }
+    CAL_TRY(upload_csr(c, n, rowptr, col, val, blk, max_nnz));
     if (A.herm) {
         CAL_HIP(c, hipMalloc((void**)&A.vim, std::max<int64_t>(A.nnz, 1) * sizeof(double)));
         if (A.nnz > 0) CAL_HIP(c, hipMemcpy(A.vim, vim, A.nnz * sizeof(double), hipMemcpyHostToDevice));
     }
-    CAL_HIP(c, hipMemcpy(A.blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
     c->has_A = true;
     c->A_gen++;
     return 0;
@@ -808,37 +803,6 @@ int shared_format_only_stacked(cal_ctx* c, const char* who) {
                      std::string(who) + ": the \"shared\" format stores H of blkdiag(H, H) once on one rank; its only "
                                         "ways of setting a matrix are cal_set_matrix_csr_stacked and "
                                         "cal_set_matrix_csr_hermitian");
-}
-
-// the launch description of the shared stacked SpMV (H's arrays, 2 n_half-row vectors)
-static SpmvArgs shared_args(const DevMatrix& A, const double* x, double* y, int mode) {
-    SpmvArgs a;
-    a.rowptr = A.rowptr;
-    a.col = A.col;
-    a.val = A.val;
-    a.blk = A.blk;
-    a.nblk = A.nblk;
-    a.x = x;
-    a.y = y;
-    a.xprev = nullptr;
-    a.shift = 0.0;
-    a.im2 = 0.0;
-    a.xcd = 1;
-    a.mode = mode | (A.nit << 8);
-    // col + val (+ vim) of H against the 256 MB Infinity Cache
-    a.nt = (int64_t)(A.herm ? 20 : 12) * A.nnz > ((int64_t)256 << 20) ? 1 : 0;
-    return a;
-}
-
-// the stored-once SpMV of the matrix: k_spmv_herm on E(H), k_spmv_shared on blkdiag(H, H)
-static hipError_t launch_stored_once(const DevMatrix& A, const SpmvArgs& a, hipStream_t st) {
-    return A.herm ? launch_spmv_herm(a, A.vim, A.n_half, st) : launch_spmv_shared(a, A.n_half, st);
-}
-
-// algorithmic bytes of a shared SpMV: H's col / val (/ vim) / rowptr once, x and
-// y of both halves, and the previous power / Lanczos vector when there is one
-static double shared_spmv_bytes(const DevMatrix& A, bool prev) {
-    return (A.herm ? 20.0 : 12.0) * A.nnz + 4.0 * (A.n_half + 1) + 32.0 * A.n_half + (prev ? 16.0 * A.n_half : 0.0);
 }
 
 // ---- the stored diagonal as a device vector ---------------------------------
@@ -1012,10 +976,6 @@ static PatArgs dsplit_args(const DevMatrix& A, const double* x, double* y, int m
     return p;
 }
 
-// algorithmic bytes of a diagonal-split SpMV: the mask key, the diagonal, x
-// and y per row, and the previous power / Lanczos vector when there is one
-static double dsplit_spmv_bytes(int64_t len, bool prev) { return (double)len * (1 + 8 + 16 + (prev ? 8 : 0)); }
-
 static PatArgs pat_args(const DevMatrix& A, int64_t o, int64_t len, const double* x, double* y, int mode,
                         double shift, double im2, const double* xprev) {
     const int64_t d = o - A.ext_off;  // launch origin relative to the local origin
@@ -1069,11 +1029,105 @@ static PatArgs pat_args(const DevMatrix& A, int64_t o, int64_t len, const double
     return p;
 }
 
-// algorithmic bytes of a row-pattern SpMV over len rows: the key (1 B per row
-// with pair patterns / the plane march's keys, 2 B otherwise), x, y, and
-// the previous power for MODE 2
-static double pat_spmv_bytes(const DevMatrix& A, int64_t len, int mode) {
-    return (double)len * ((A.use_pair ? 1 : 2) + 16 + (mode == 2 ? 8 : 0));
+// ---- the SpMV dispatch -------------------------------------------------------
+// The storage that serves an SpMV of mode `mode` (DevMatrix's flags, read
+// here and nowhere else in the dispatch).  The diagonal-split kernel has no
+// mode 3 (normest), which goes to the CSR arrays the matrix also keeps.
+enum class SpmvStore { stacked, pat, dsplit, csr };
+static SpmvStore spmv_store(const DevMatrix& A, int mode) {
+    if (A.shared) return SpmvStore::stacked;
+    if (A.use_pat) return SpmvStore::pat;
+    return A.use_dsplit && mode != 3 ? SpmvStore::dsplit : SpmvStore::csr;
+}
+
+// col / val stream once per SpMV: non-temporal loads when they are larger than
+// the 256 MB Infinity Cache (12 stored bytes per nonzero, 20 with vim)
+static int spmv_nt(const DevMatrix& A) { return (int64_t)(A.herm ? 20 : 12) * A.nnz > ((int64_t)256 << 20) ? 1 : 0; }
+
+// Algorithmic bytes of an SpMV over len rows (a sub-range on the row patterns
+// only), prev: with the previous power / Lanczos vector.
+//   stacked  H's col / val (/ vim) / rowptr once, x and y of both halves
+//   pat      the key (1 B per row with pair patterns / the plane march's keys,
+//            2 B otherwise), x, y
+//   dsplit   the mask key, the diagonal, x and y per row
+//   csr      12 nnz + 20 n + 4
+static double spmv_bytes(const DevMatrix& A, SpmvStore k, int64_t len, bool prev) {
+    switch (k) {
+        case SpmvStore::stacked:
+            return (A.herm ? 20.0 : 12.0) * A.nnz + 4.0 * (A.n_half + 1) + 32.0 * A.n_half +
+                   (prev ? 16.0 * A.n_half : 0.0);
+        case SpmvStore::pat: return (double)len * ((A.use_pair ? 1 : 2) + 16 + (prev ? 8 : 0));
+        case SpmvStore::dsplit: return (double)len * (1 + 8 + 16 + (prev ? 8 : 0));
+        default: return 12.0 * A.nnz + 20.0 * len + 4.0 + (prev ? 8.0 * len : 0.0);
+    }
+}
+
+// One SpMV over the local rows, as the kernels take it (SpmvArgs' fields)
+struct SpmvCall {
+    const double* x;
+    double* y;
+    int mode;
+    double shift, im2;
+    const double *xprev, *xnrm, *pb2;
+    double* dotp;
+};
+
+// the CSR launch description (k_spmv; k_spmv_stacked with H's arrays and blocks)
+static SpmvArgs spmv_args(const DevMatrix& A, const SpmvCall& s) {
+    SpmvArgs a;
+    a.rowptr = A.rowptr;
+    a.col = A.col;
+    a.val = A.val;
+    a.blk = A.blk;
+    a.nblk = A.nblk;
+    a.x = s.x;
+    a.y = s.y;
+    a.xprev = s.xprev;
+    a.shift = s.shift;
+    a.im2 = s.im2;
+    a.mode = s.mode | (A.nit << 8);
+    a.xnrm = s.xnrm;
+    a.xcd = 1;
+    a.nt = spmv_nt(A);
+    a.pb2 = s.pb2;
+    a.dotp = s.dotp;
+    return a;
+}
+
+// Launch s on st from the matrix's storage.  timed: the context whose SpMV
+// timer brackets the launch and whose row count it bumps (st its stream), or
+// null for neither.  The callers check the mode; a kernel that is not built
+// for it answers hipErrorInvalidValue.
+static hipError_t spmv_launch(const DevMatrix& A, const SpmvCall& s, hipStream_t st, cal_ctx* timed) {
+    const SpmvStore k = spmv_store(A, s.mode);
+    int t = -1;
+    if (timed) {
+        timed->stat_spmv_rows += A.n_local;
+        t = timer_begin(timed, 0, spmv_bytes(A, k, A.n_local, s.xprev != nullptr));
+    }
+    hipError_t e;
+    if (k == SpmvStore::stacked) {
+        e = launch_spmv_stacked(spmv_args(A, s), A.vim, A.n_half, st);
+    } else if (k == SpmvStore::csr) {
+        e = launch_spmv(spmv_args(A, s), st);
+    } else {
+        PatArgs p = k == SpmvStore::pat ? pat_args(A, A.ext_off, A.n_local, s.x, s.y, s.mode, s.shift, s.im2, s.xprev)
+                                        : dsplit_args(A, s.x, s.y, s.mode, s.shift, s.im2, s.xprev);
+        p.pb2 = s.pb2;
+        p.dotp = s.dotp;
+        e = k == SpmvStore::pat ? launch_spmv_pat(p, st) : launch_spmv_dsplit(p, st);
+    }
+    if (e == hipSuccess) timer_end(timed, t);
+    return e;
+}
+
+// a row-pattern launch over a sub-range of the stored rows, timed and counted
+static int spmv_pat_timed(cal_ctx* c, const PatArgs& p) {
+    c->stat_spmv_rows += p.n;
+    const int t = timer_begin(c, 0, spmv_bytes(c->A, SpmvStore::pat, p.n, p.mode == 2));
+    CAL_HIP(c, launch_spmv_pat(p, c->stream));
+    timer_end(c, t);
+    return 0;
 }
 
 int spmv_range(cal_ctx* c, int64_t o, int64_t len, const double* x, double* y, int mode, double shift, double im2,
@@ -1081,41 +1135,18 @@ int spmv_range(cal_ctx* c, int64_t o, int64_t len, const double* x, double* y, i
     const DevMatrix& A = c->A;
     if (o < 0 || (o & 1) || len < 0 || o + len > A.n_rows)
         return set_error(c, CAL_ERR_ARG, "spmv_range: bad stored-row range");
-    const PatArgs p = pat_args(A, o, len, x, y, mode, shift, im2, xprev);
-    c->stat_spmv_rows += len;
-    const int t = timer_begin(c, 0, pat_spmv_bytes(A, len, mode));
-    CAL_HIP(c, launch_spmv_pat(p, c->stream));
-    timer_end(c, t);
-    return 0;
+    return spmv_pat_timed(c, pat_args(A, o, len, x, y, mode, shift, im2, xprev));
 }
 
-// y = A x on stream st, no timer and no statistics: the asynchronous normest
-// (lanczos.cpp) on its own stream beside the solver's.  One rank (no halo).
-// Mode 0, or 3 on CSR (y = A (x / sqrt(*xnrm))).
+// y = A x on stream st, no timer, no statistics and no halo exchange: the
+// asynchronous normest (lanczos.cpp) on its own stream beside the solver's.
+// One rank.  Mode 0, or 3 on CSR (y = A (x / sqrt(*xnrm))).
 hipError_t spmv_on_stream(const cal_ctx* c, const double* x, double* y, int mode, const double* xnrm, hipStream_t st) {
     const DevMatrix& A = c->A;
     if (mode != 0 && mode != 3) return hipErrorInvalidValue;
     if (A.shared) return hipErrorInvalidValue;  // normest's stream: refused before it starts (shared_refuses)
-    if (A.use_pat) {
-        if (mode != 0) return hipErrorInvalidValue;
-        return launch_spmv_pat(pat_args(A, A.ext_off, A.n_local, x, y, 0, 0.0, 0.0, nullptr), st);
-    }
-    if (A.use_dsplit && mode == 0) return launch_spmv_dsplit(dsplit_args(A, x, y, 0, 0.0, 0.0, nullptr), st);
-    SpmvArgs a;
-    a.rowptr = A.rowptr;
-    a.col = A.col;
-    a.val = A.val;
-    a.blk = A.blk;
-    a.nblk = A.nblk;
-    a.x = x;
-    a.y = y;
-    a.xprev = nullptr;
-    a.shift = 0.0;
-    a.im2 = 0.0;
-    a.xnrm = xnrm;
-    a.mode = mode | (A.nit << 8);
-    a.nt = (int64_t)12 * A.nnz > ((int64_t)256 << 20) ? 1 : 0;
-    return launch_spmv(a, st);
+    if (A.use_pat && mode != 0) return hipErrorInvalidValue;
+    return spmv_launch(A, SpmvCall{x, y, mode, 0.0, 0.0, nullptr, xnrm, nullptr, nullptr}, st, nullptr);
 }
 
 int spmv_resid_pair_blocks(cal_ctx* c) {
@@ -1168,60 +1199,24 @@ int spmv_range2(cal_ctx* c, int64_t o1, int64_t len1, int64_t o2, int64_t len2, 
     PatArgs p = pat_args(A, o1, len1 + len2, x, y, mode, shift, im2, xprev);
     p.gap_at = len1 / 2;
     p.gap = (o2 - o1) / 2 - p.gap_at;
-    c->stat_spmv_rows += len1 + len2;
-    const int t = timer_begin(c, 0, pat_spmv_bytes(A, len1 + len2, mode));
-    CAL_HIP(c, launch_spmv_pat(p, c->stream));
-    timer_end(c, t);
-    return 0;
+    return spmv_pat_timed(c, p);
 }
 
 int spmv_dev(cal_ctx* c, const double* x, double* y, int mode, double shift, double im2, const double* xprev,
              const double* xnrm) {
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
     if (mode == 3 && (c->A.use_pat || !xnrm)) return set_error(c, CAL_ERR_ARG, "spmv_dev: mode 3 needs CSR and xnrm");
-    if (c->A.shared) {
+    const SpmvStore k = spmv_store(c->A, mode);
+    // the stored-once formats run on one rank: no halo
+    if (k == SpmvStore::stacked) {
         if (mode == 3) return shared_refuses(c, "normest");
-        if (mode < 0 || mode > 2 || (mode == 2 && !xprev)) return set_error(c, CAL_ERR_ARG, "spmv_dev: bad mode");
-        SpmvArgs a = shared_args(c->A, x, y, mode);
-        a.xprev = mode == 2 ? xprev : nullptr;
-        a.shift = shift;
-        a.im2 = im2;
-        c->stat_spmv_rows += c->A.n_local;
-        const int t = timer_begin(c, 0, shared_spmv_bytes(c->A, mode == 2));
-        CAL_HIP(c, launch_stored_once(c->A, a, c->stream));
-        timer_end(c, t);
-        return 0;
+    } else {
+        CAL_TRY(halo_exchange(c, const_cast<double*>(x)));
     }
-    CAL_TRY(halo_exchange(c, const_cast<double*>(x)));
-    if (c->A.use_pat) return spmv_range(c, c->A.ext_off, c->A.n_local, x, y, mode, shift, im2, xprev);
-    if (c->A.use_dsplit && mode != 3) {
-        if (mode < 0 || mode > 2 || (mode == 2 && !xprev)) return set_error(c, CAL_ERR_ARG, "spmv_dev: bad mode");
-        c->stat_spmv_rows += c->A.n_local;
-        const int t = timer_begin(c, 0, dsplit_spmv_bytes(c->A.n_local, mode == 2));
-        CAL_HIP(c, launch_spmv_dsplit(dsplit_args(c->A, x, y, mode, shift, im2, mode == 2 ? xprev : nullptr), c->stream));
-        timer_end(c, t);
-        return 0;
-    }
-    SpmvArgs a;
-    a.xnrm = xnrm;
-    a.rowptr = c->A.rowptr;
-    a.col = c->A.col;
-    a.val = c->A.val;
-    a.blk = c->A.blk;
-    a.nblk = c->A.nblk;
-    a.x = x;
-    a.y = y;
-    a.xprev = xprev;
-    a.shift = shift;
-    a.im2 = im2;
-    a.mode = mode | (c->A.nit << 8);
-    // col + val of the stored rows against the 256 MB Infinity Cache
-    a.nt = (int64_t)12 * c->A.nnz > ((int64_t)256 << 20) ? 1 : 0;
-    c->stat_spmv_rows += c->A.n_local;
-    // 12 nnz + 20 n + 4 (+ 8 n for the previous power, MODE 2)
-    const int t = timer_begin(c, 0, 12.0 * c->A.nnz + 20.0 * c->A.n_local + 4.0 + (mode == 2 ? 8.0 * c->A.n_local : 0.0));
-    CAL_HIP(c, launch_spmv(a, c->stream));
-    timer_end(c, t);
+    if ((k == SpmvStore::stacked || k == SpmvStore::dsplit) && (mode < 0 || mode > 2 || (mode == 2 && !xprev)))
+        return set_error(c, CAL_ERR_ARG, "spmv_dev: bad mode");
+    const SpmvCall s{x, y, mode, shift, im2, mode == 2 ? xprev : nullptr, xnrm, nullptr, nullptr};
+    CAL_HIP(c, spmv_launch(c->A, s, c->stream, c));
     return 0;
 }
 
@@ -1229,74 +1224,25 @@ int spmv_dev(cal_ctx* c, const double* x, double* y, int mode, double shift, dou
 // null: y = A x, the bits of mode 0) and one partial of y'x per block in
 // dotp.  One rank.  spmv_lanczos_parts: the number of partials (the launch's
 // grid), 0 when the matrix sits on the unfused row-pattern kernels.
-static SpmvArgs csr_args(const cal_ctx* c, const double* x, double* y, int mode) {
-    SpmvArgs a;
-    a.rowptr = c->A.rowptr;
-    a.col = c->A.col;
-    a.val = c->A.val;
-    a.blk = c->A.blk;
-    a.nblk = c->A.nblk;
-    a.x = x;
-    a.y = y;
-    a.xprev = nullptr;
-    a.shift = 0.0;
-    a.im2 = 0.0;
-    a.mode = mode | (c->A.nit << 8);
-    a.nt = (int64_t)12 * c->A.nnz > ((int64_t)256 << 20) ? 1 : 0;
-    return a;
-}
-
 int spmv_lanczos_parts(const cal_ctx* c, const double* x, const double* xprev, double* y) {
     const DevMatrix& A = c->A;
     if (!c->has_A || (c->comm && c->comm->nranks > 1)) return 0;
-    if (A.shared) return 2 * A.nblk;  // the top half's block partials, then the bottom half's
-    if (A.use_dsplit) return spmv_dsplit_blocks(dsplit_args(A, x, y, 4, 0.0, 0.0, xprev));
-    if (!A.use_pat) return spmv_lanczos_blocks(csr_args(c, x, y, 4));
-    return spmv_pat_lanczos_blocks(pat_args(A, A.ext_off, A.n_local, x, y, 4, 0.0, 0.0, xprev));
+    switch (spmv_store(A, 4)) {
+        case SpmvStore::stacked: return 2 * A.nblk;  // the top half's block partials, then the bottom half's
+        case SpmvStore::dsplit: return spmv_dsplit_blocks(dsplit_args(A, x, y, 4, 0.0, 0.0, xprev));
+        case SpmvStore::pat:
+            return spmv_pat_lanczos_blocks(pat_args(A, A.ext_off, A.n_local, x, y, 4, 0.0, 0.0, xprev));
+        default: return spmv_lanczos_blocks(spmv_args(A, SpmvCall{x, y, 4, 0.0, 0.0, xprev, nullptr, nullptr, nullptr}));
+    }
 }
 
 int spmv_lanczos_dev(cal_ctx* c, const double* x, const double* xprev, const double* pb2, double* y, double* dotp) {
-    const DevMatrix& A = c->A;
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
     if (spmv_lanczos_parts(c, x, xprev, y) <= 0 || !dotp)
         return set_error(c, CAL_ERR_ARG, "spmv_lanczos_dev: no fused Lanczos mode for this matrix");
     const bool has = xprev && pb2;
-    c->stat_spmv_rows += A.n_local;
-    if (A.shared) {
-        SpmvArgs a = shared_args(A, x, y, 4);
-        a.xprev = has ? xprev : nullptr;
-        a.pb2 = has ? pb2 : nullptr;
-        a.dotp = dotp;
-        const int t = timer_begin(c, 0, shared_spmv_bytes(A, has));
-        CAL_HIP(c, launch_stored_once(A, a, c->stream));
-        timer_end(c, t);
-        return 0;
-    }
-    if (A.use_pat) {
-        PatArgs p = pat_args(A, A.ext_off, A.n_local, x, y, 4, 0.0, 0.0, has ? xprev : nullptr);
-        p.pb2 = has ? pb2 : nullptr;
-        p.dotp = dotp;
-        const int t = timer_begin(c, 0, pat_spmv_bytes(A, A.n_local, has ? 2 : 0));
-        CAL_HIP(c, launch_spmv_pat(p, c->stream));
-        timer_end(c, t);
-        return 0;
-    }
-    if (A.use_dsplit) {
-        PatArgs p = dsplit_args(A, x, y, 4, 0.0, 0.0, has ? xprev : nullptr);
-        p.pb2 = has ? pb2 : nullptr;
-        p.dotp = dotp;
-        const int t = timer_begin(c, 0, dsplit_spmv_bytes(A.n_local, has));
-        CAL_HIP(c, launch_spmv_dsplit(p, c->stream));
-        timer_end(c, t);
-        return 0;
-    }
-    SpmvArgs a = csr_args(c, x, y, 4);
-    a.xprev = has ? xprev : nullptr;
-    a.pb2 = has ? pb2 : nullptr;
-    a.dotp = dotp;
-    const int t = timer_begin(c, 0, 12.0 * A.nnz + 20.0 * A.n_local + 4.0 + (has ? 8.0 * A.n_local : 0.0));
-    CAL_HIP(c, launch_spmv(a, c->stream));
-    timer_end(c, t);
+    const SpmvCall s{x, y, 4, 0.0, 0.0, has ? xprev : nullptr, nullptr, has ? pb2 : nullptr, dotp};
+    CAL_HIP(c, spmv_launch(c->A, s, c->stream, c));
     return 0;
 }
 

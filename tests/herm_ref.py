@@ -1,4 +1,4 @@
-"""NumPy references of the Hermitian stored-once SpMV (k_spmv_herm;
+"""NumPy references of the Hermitian stored-once SpMV (k_spmv_stacked, HERM true;
 test_hermitian_host.py, test_gpu_hermitian.py): y = E(H) x with E(H) =
 [[A, -B], [B, A]] for the complex Hermitian CSR H = A + iB on the stacked
 vector x = [x0; x1] of 2n rows.
@@ -44,7 +44,7 @@ def _rowsums(indptr, terms):
 
 
 def herm_chain(H, x, val_im=None):
-    """y = E(H) x in k_spmv_herm's order.  val_im replaces H's imaginary parts
+    """y = E(H) x in k_spmv_stacked's order (HERM true).  val_im replaces H's imaginary parts
     (e.g. zeros: the Hermitian path on a real matrix)."""
     n = H.shape[0]
     a, b = _parts(H)

@@ -1,5 +1,5 @@
 """Complex Hermitian H on the device: cal_set_matrix_csr_hermitian, the
-stored-once kernel k_spmv_herm ("shared" selected) and the host-built embedding
+stored-once kernel k_spmv_stacked with HERM ("shared" selected) and the host-built embedding
 E(H) = [[A, -B], [B, A]] on the existing kernels ("csr"), through the SpMV
 modes, standard Lanczos and the whole time propagator.
 

@@ -1,4 +1,4 @@
-"""The shared stacked SpMV format (``spmv_format="shared"``, kernel k_spmv_shared):
+"""The shared stacked SpMV format (``spmv_format="shared"``, kernel k_spmv_stacked, HERM false):
 blkdiag(H, H) with H stored once.
 
 Everything here compares a "shared" context against a "csr" context given the

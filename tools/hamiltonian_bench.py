@@ -20,7 +20,7 @@ each in a fresh child process, alternating, --rounds times each:
          matrix, shared's A/B partner, same legs on the same 2n rows
   herm   Context(spmv_format="shared").set_matrix_hermitian(H) with H =
          peierls_hamiltonian on N^3 (the same potential, flux 1/16 per
-         plaquette): the complex Hermitian H stored once (k_spmv_herm), the
+         plaquette): the complex Hermitian H stored once (k_spmv_stacked, HERM true), the
          stacked legs on the 2n rows of [[A, -B], [B, A]]
   herm_csr  the same H with spmv_format="csr": the host-built embedding on the
          existing CSR kernel, herm's A/B partner ("herm_vs_herm_csr"; "herm_vs_shared"
