@@ -23,6 +23,8 @@ from .api import (  # noqa: F401
     drive_rows,
     eig,
     expm_col1,
+    expm_real_col1,
+    ground_state,
     lanczos,
     lanczos_ex,
     leja,

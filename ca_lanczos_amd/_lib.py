@@ -165,6 +165,11 @@ SIGNATURES = [
     ("cal_prop_refresh_shifts", c_int, [c_void_p]),
     ("cal_prop_set_nonlinear", c_int, [c_void_p, c_double, c_char_p]),
     ("cal_prop_get_nonlinear", c_int, [c_void_p, c_int64, c_int64, dp, POINTER(c_int64)]),
+    ("cal_prop_begin_real", c_int, [c_void_p, c_int64, dp, c_int, c_int, c_char_p, dp, c_int]),
+    ("cal_prop_set_imaginary_time", c_int, [c_void_p, c_int]),
+    ("cal_prop_get_energetics", c_int, [c_void_p, c_int64, c_int64, dp, POINTER(c_int64)]),
+    ("cal_prop_combine_real", c_int, [c_void_p, c_int64, c_int, dp, dp, c_int, dp, dp, dp, dp]),
+    ("cal_prop_combine_real_ld", c_int, [c_void_p, c_int64, c_int, dp, c_int64, dp, c_int, dp, dp, dp, dp]),
     ("cal_ca_lanczos_prop", c_int,
      [c_void_p, c_int64, dp, dp, c_int, c_int, c_double, c_double, c_char_p, dp, c_int, c_int, dp, dp, dp, ip]),
     ("cal_lanczos", c_int, [c_void_p, dp, c_int, c_char_p, c_int, dp, dp, dp, dp, POINTER(StdLanczosInfo)]),
@@ -187,6 +192,7 @@ SIGNATURES = [
     ("cal_tridiag_eigvals", c_int, [c_int, dp, dp, dp]),
     ("cal_qrstep", c_int, [c_int, dp, c_int, dp, c_int, c_double]),
     ("cal_expm_col1", c_int, [c_int, dp, c_int, c_double, dp, dp]),
+    ("cal_expm_real_col1", c_int, [c_int, dp, c_int, c_double, dp]),
 ]
 
 for _name, _res, _args in SIGNATURES:

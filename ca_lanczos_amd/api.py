@@ -296,6 +296,34 @@ class Context:
         observables are those of out."""
         return self._prop_combine(Q, c, mask, W, phi, "prop_combine_masked")
 
+    def prop_combine_real(self, Q, a, W=None):
+        """The real state's combine sweep on host data
+        (cal_prop_combine_real): Q is n x m real, a real with m entries;
+        ``out[i] = sum_j Q[i, j] a_j`` as one chain per row over ascending j.
+        W: real diagonal operators (a list or n x nw, at most 4).  Returns
+        (out, norm2 = sum out^2, <W_k> = sum W_k out^2 (nw)).  A Q that is a
+        column-major view with a column stride above n (``big[:n, :]``) keeps
+        that leading dimension on the device: an odd one runs the kernel's
+        8-byte path."""
+        Q = np.asarray(Q, dtype=np.float64)
+        if Q.ndim != 2:
+            raise ValueError("Q must be n x m")
+        n, m = Q.shape
+        it = Q.itemsize
+        if not (n >= 1 and Q.strides[0] == it and Q.strides[1] >= n * it and Q.strides[1] % it == 0):
+            Q = f64(Q)
+        ldq = Q.strides[1] // it if m > 1 or Q.strides[1] >= n * it else n
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.shape[0] != m:
+            raise ValueError("a needs one entry per column of Q")
+        Wm = _obs_arrays(n, W, None)[0]
+        nw = Wm.shape[1]
+        out, sums, n2 = np.zeros(n), np.zeros(max(nw, 1)), ctypes.c_double()
+        check(self.h, lib.cal_prop_combine_real_ld(self.h, n, m, ptr(Q), ldq, ptr(a), nw, ptr(Wm) if nw else None,
+                                                   ptr(out), ctypes.cast(ctypes.byref(n2), dp), ptr(sums)),
+              "prop_combine_real")
+        return out, n2.value, sums[:nw].copy()
+
     def set_diagonal(self, d):
         """Rewrite the stored diagonal of the resident matrix in place
         (cal_set_diagonal): one entry per row, no new upload or analysis.
@@ -937,6 +965,19 @@ def expm_col1(T, dt):
     return cre[:m] + 1j * cim[:m]
 
 
+def expm_real_col1(T, tau):
+    """``expm(-tau*(T - T(1,1)*I))(:,1)`` for a general real square T
+    (cal_expm_real_col1: host only; the coefficients of an imaginary-time
+    step, which uses their direction only)."""
+    T = f64(T)
+    m = T.shape[0]
+    c = np.zeros(max(m, 1))
+    st = lib.cal_expm_real_col1(m, ptr(T), max(m, 1), float(tau), ptr(c))
+    if st != 0:
+        raise CalError(st, "cal_expm_real_col1")
+    return c[:m]
+
+
 def _split(psi):
     psi = np.asarray(psi)
     re = np.ascontiguousarray(psi.real, dtype=np.float64).ravel()
@@ -1011,17 +1052,33 @@ class Propagator:
     frames); the state lives on the device as [Re psi; Im psi].  Observables,
     energy, absorber, drive and the nonlinear term touch only the real
     diagonal and work on either.  ``state()`` is the only copy back of the
-    state, ``set_observables`` / ``observables`` watch it from the device."""
+    state, ``set_observables`` / ``observables`` watch it from the device.
 
-    def __init__(self, H, psi0, s, max_blocks, basis="newton", eigest=None, ctx=None):
+    ``set_imaginary_time`` turns the stepper into ``psi <- sqrt(N) exp(-tau
+    H[psi]) psi / ||.||`` (ground states; ``ground_state`` drives it), and
+    ``energetics`` gives mu, the Gross-Pitaevskii energy and the
+    eigen-residual of every step's start state in either mode.
+    ``real=True`` (a real H and a real psi0) is the real-state path
+    (cal_prop_begin_real): imaginary time only, on the n x n H itself through
+    ``Context.set_matrix`` in any SpMV format, the state a real vector of n
+    rows -- half the bytes of every SpMV and sweep.  It takes the drive, the
+    nonlinear term, W observables and the energy; reference states, an
+    absorber and real time are refused and need the stacked propagator."""
+
+    def __init__(self, H, psi0, s, max_blocks, basis="newton", eigest=None, ctx=None, real=False):
         self.n = H.shape[0]
+        self.real = bool(real)
+        if self.real and (np.iscomplexobj(H) or np.iscomplexobj(psi0)):
+            raise ValueError("real=True needs a real H and a real psi0 (the stacked propagator takes complex ones)")
         self._nw = 0
         self._nk = 0
         self.t = 0.0  # the propagator's clock: the sum of the (sub-)steps taken through step()
         self._own = ctx is None
         self.ctx = ctx or Context()
         try:
-            if np.iscomplexobj(H):
+            if self.real:
+                self.ctx.set_matrix(H)
+            elif np.iscomplexobj(H):
                 self.ctx.set_matrix_hermitian(H)
             else:
                 self.ctx.set_matrix_stacked(H)
@@ -1029,8 +1086,12 @@ class Propagator:
             if re.shape[0] != self.n:
                 raise ValueError("psi0 must have H.shape[0] entries")
             e, ne = _eigest(eigest)
-            check(self.ctx.h, lib.cal_prop_begin(self.ctx.h, self.n, ptr(re), ptr(im), s, max_blocks,
-                                                 basis.encode(), ptr(e), ne), "prop_begin")
+            if self.real:
+                check(self.ctx.h, lib.cal_prop_begin_real(self.ctx.h, self.n, ptr(re), s, max_blocks, basis.encode(),
+                                                          ptr(e), ne), "prop_begin_real")
+            else:
+                check(self.ctx.h, lib.cal_prop_begin(self.ctx.h, self.n, ptr(re), ptr(im), s, max_blocks,
+                                                     basis.encode(), ptr(e), ne), "prop_begin")
         except Exception:
             if self._own:
                 self.ctx.close()
@@ -1097,9 +1158,10 @@ class Propagator:
         from ``psi_n`` under ``g (|psi_n|^2 + |psi*|^2)/2`` (second order, two
         builds per step).  ``g = 0`` switches the term off; H0's diagonal goes
         back when neither the term nor a drive is set.  Clears ``nonlinear()``.
-        Not built: the conserved Gross-Pitaevskii energy as an observable
-        (``energy`` stays ``<psi|H|psi>`` with the H stored in the matrix)
-        and more than second order in the nonlinear part."""
+        The conserved Gross-Pitaevskii energy is a column of
+        ``energetics()`` (the ``energy`` observable stays ``<psi|H|psi>``
+        with the H stored in the matrix).  Not built: more than second order
+        in the nonlinear part."""
         if not getattr(self, "_open", False):
             raise CalError(_lib.CAL_ERR_ARG, "set_nonlinear: the propagator is closed")
         check(self.ctx.h, lib.cal_prop_set_nonlinear(self.ctx.h, float(g), str(density).encode()),
@@ -1118,6 +1180,35 @@ class Propagator:
         check(self.ctx.h, lib.cal_prop_get_nonlinear(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr)),
               "prop_get_nonlinear")
         return rows
+
+    def set_imaginary_time(self, on=True):
+        """From now on ``step`` takes ``dt`` as an imaginary-time step tau:
+        ``psi <- sqrt(N) exp(-tau H[psi]) psi / ||.||`` with N the squared
+        norm of the state at this call -- the iteration whose fixed point is
+        the ground state (of the Gross-Pitaevskii functional under
+        ``set_nonlinear``).  Everything else (drive, nonlinear densities,
+        observables, absorber) keeps its meaning.  ``on=False`` returns to
+        real time; a ``real=True`` propagator refuses that."""
+        check(self.ctx.h, lib.cal_prop_set_imaginary_time(self.ctx.h, 1 if on else 0), "prop_set_imaginary_time")
+        return self
+
+    def energetics(self, first=0, count=None):
+        """One entry per completed step since the propagator was opened (rows
+        [first, first + count); default all), of the state psi_n the step
+        started from: dict of ``t``, ``norm2`` (N_n), ``mu`` (the Rayleigh
+        quotient ``<psi_n|H[psi_n]|psi_n>/N_n``, the chemical potential),
+        ``energy`` (``N_n mu - (g/2) sum |psi_n|^4``, the Gross-Pitaevskii
+        energy: conserved in real time) and ``residual``
+        (``||H[psi_n] psi_n - mu psi_n|| / sqrt(N_n)``).  They are read off
+        the first column of the step's Krylov matrix: no kernel, no sweep."""
+        nr = ctypes.c_int64()
+        check(self.ctx.h, lib.cal_prop_get_energetics(self.ctx.h, 0, 0, None, ctypes.byref(nr)), "prop_get_energetics")
+        count = nr.value - first if count is None else count
+        rows = np.zeros((max(count, 0), 5))
+        check(self.ctx.h, lib.cal_prop_get_energetics(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr)),
+              "prop_get_energetics")
+        return dict(t=rows[:, 0].copy(), norm2=rows[:, 1].copy(), mu=rows[:, 2].copy(), energy=rows[:, 3].copy(),
+                    residual=rows[:, 4].copy())
 
     def refresh_shifts(self):
         """Forget the Newton shifts of the first step: the next step computes
@@ -1218,6 +1309,78 @@ class Propagator:
             self.close()
         except Exception:
             pass
+
+
+def _ground_state_loop(step, last, state, tol, max_steps):
+    """The stopping rule of ``ground_state``: ``step()`` takes one
+    imaginary-time step and returns its status, ``last()`` the energetics
+    rows recorded so far as a dict, ``state()`` the current state.  A step's
+    row describes the state it started from, so the loop stops when that
+    row's ``residual <= tol * max(1, |mu|)`` -- the state returned is one
+    step past the one judged, and no worse.  A CAL_WARN_BREAKDOWN whose last
+    recorded row already meets the criterion counts as converged (an
+    eigenvector to rounding has a one-dimensional Krylov space)."""
+    def met(h):
+        return len(h["mu"]) > 0 and h["residual"][-1] <= tol * max(1.0, abs(h["mu"][-1]))
+    steps, converged = 0, False
+    h = last()
+    while steps < max_steps:
+        st = step()
+        h = last()
+        if st == _lib.CAL_WARN_BREAKDOWN:
+            converged = met(h)
+            break
+        steps += 1
+        if met(h):
+            converged = True
+            break
+    k = len(h["mu"]) - 1
+    nan = float("nan")
+    return dict(psi=state(), mu=h["mu"][k] if k >= 0 else nan, energy=h["energy"][k] if k >= 0 else nan,
+                residual=h["residual"][k] if k >= 0 else nan, steps=steps, converged=converged, history=h)
+
+
+def ground_state(H, psi0, tau, s, max_blocks, g=0.0, density="frozen", tol=1e-10, max_steps=1000, real=None,
+                 basis="newton", ctx=None):
+    """The ground state of H (of the Gross-Pitaevskii functional with
+    ``g != 0``) by imaginary-time propagation on the device, normalised to
+    ``||psi0||``.  ``real=None`` takes the real-state path exactly when H and
+    psi0 are real.  One step at a time until ``residual <= tol * max(1,
+    |mu|)`` or ``max_steps``.  Returns a dict: ``psi``, ``mu``, ``energy``,
+    ``residual``, ``steps``, ``converged`` and ``history`` (the energetics
+    rows; mu, energy and residual are the last row's, of the state before the
+    last step).
+
+    The nonlinear term rewrites the matrix's stored diagonal, which only the
+    "csr" and "split" formats keep.  On the real path H goes up through
+    ``Context.set_matrix``, where "auto" may pick a format without one and
+    ``set_nonlinear`` is then refused; so with ``g != 0``, ``real`` and no
+    ``ctx`` the context opened here is a "csr" one.  Pass a
+    ``Context(spmv_format="split")`` for a grid Hamiltonian that qualifies."""
+    if real is None:
+        real = not (np.iscomplexobj(H) or np.iscomplexobj(psi0))
+    own = None
+    if ctx is None and real and g != 0.0:
+        ctx = own = Context(spmv_format="csr")
+    try:
+        P = Propagator(H, psi0, s, max_blocks, basis=basis, ctx=ctx, real=real)
+    except Exception:
+        if own is not None:
+            own.close()
+        raise
+    try:
+        if not real:
+            P.set_imaginary_time(True)
+        if g != 0.0:
+            P.set_nonlinear(g, density)
+        out = _ground_state_loop(lambda: P.step(tau), P.energetics, P.state, tol, max_steps)
+        if real:
+            out["psi"] = out["psi"].real.copy()
+        return out
+    finally:
+        P.close()
+        if own is not None:
+            own.close()
 
 
 def ca_lanczos_prop(A, r0, s, m, dt, tol=1.0e-10, basis="newton", eigest=None, adaptive=False, ctx=None):

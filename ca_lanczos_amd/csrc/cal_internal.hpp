@@ -584,6 +584,10 @@ struct PropCombine {
     PropObs obs;                   // zero counts: none
     const double* mask = nullptr;  // null: none
     int64_t ldm = 0;
+    // a real state (k_prop_combine_real): out[i] = sum_j Q[i,j] a_j for i < n,
+    // ld >= n, b unused, nw observables allowed (the chain d = t*t;
+    // acc = acc + W_k[i]*d), no reference states and no mask
+    bool real = false;
 };
 int prop_combine_blocks(int64_t n);
 int prop_combine_quantities(const PropCombine& p);
@@ -631,6 +635,9 @@ struct DiagDensity {
     const double* B = nullptr;  // null: one state
     double ga = 0.0, gb = 0.0;
     double* partial = nullptr;
+    // real states of n rows (cal_prop_begin_real): ra = ua*ua, rb = ub*ub, no
+    // lower half is read; d.halves must be 1
+    bool real = false;
 };
 int diag_density_blocks(int64_t n);
 hipError_t launch_diag_density(const DiagDensity& a, hipStream_t st);
@@ -972,6 +979,7 @@ int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int
 // non-null), A / B stacked device states of 2n doubles; the blocks' shares of
 // sum_i |A_i|^4 go to partial (diag_density_blocks(n) doubles, the caller's).
 // Same positions, same rule for a shared matrix, timed as the drive is.
+// halves = 1: A_dev / B_dev are real states of n rows (DiagDensity::real).
 int diag_density_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
                      const double* f, const double* A_dev, double ga, const double* B_dev, double gb, double* partial);
 // dst[i] = val[dpos[i]], i < cnt <= n_local (device dst; enqueued)

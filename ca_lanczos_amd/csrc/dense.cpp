@@ -916,5 +916,89 @@ bool expm_col1(int m, const double* T, int ldt, double dt, double* c_re, double*
     return true;
 }
 
+// ---- first column of expm(-tau (T - T(1,1) I)) (imaginary-time propagation) ----
+namespace {
+// C = A B (m x m, column-major, ld m), zero entries of B skipped as in cmatmul
+void rmatmul(int m, const double* A, const double* B, double* C) {
+    for (int j = 0; j < m; ++j) {
+        double* cj = C + (size_t)j * m;
+        for (int i = 0; i < m; ++i) cj[i] = 0.0;
+        for (int k = 0; k < m; ++k) {
+            const double b = B[k + (size_t)j * m];
+            if (b == 0.0) continue;
+            const double* ak = A + (size_t)k * m;
+            for (int i = 0; i < m; ++i) cj[i] += ak[i] * b;
+        }
+    }
+}
+double rnorm1(int m, const double* A) {
+    double nrm = 0.0;
+    for (int j = 0; j < m; ++j) {
+        double cs = 0.0;
+        for (int i = 0; i < m; ++i) cs += std::fabs(A[i + (size_t)j * m]);
+        nrm = std::max(nrm, cs);
+    }
+    return nrm;
+}
+}  // namespace
+
+bool expm_real_col1(int m, const double* T, int ldt, double tau, double* c) {
+    // expm_col1's scheme in real arithmetic: A = -tau (T - T(1,1) I) / 2^sq
+    // with ||A||_1 <= 1, the Taylor series to below the last bit, sq squarings
+    // (the last one applied to the first column only)
+    const double t11 = T[0];
+    const size_t mm = (size_t)m * m;
+    std::vector<double> A(mm), E(mm), P(mm), W(mm);
+    for (int j = 0; j < m; ++j)
+        for (int i = 0; i < m; ++i) {
+            const double t = i == j ? T[i + (size_t)j * ldt] - t11 : T[i + (size_t)j * ldt];
+            const double x = tau * t;
+            // every entry is looked at: a NaN in a block that e_1 does not couple to
+            // would reach neither the norm below (max drops it) nor the first column
+            if (!std::isfinite(x)) return false;
+            A[i + (size_t)j * m] = x == 0.0 ? 0.0 : -x;
+        }
+    const double nrm = rnorm1(m, A.data());
+    if (!std::isfinite(nrm)) return false;
+    int sq = 0;
+    if (nrm > 1.0) {
+        std::frexp(nrm, &sq);  // nrm = f 2^sq, f in [0.5, 1)
+        if (sq > 1000) return false;
+    }
+    const double scale = std::ldexp(1.0, -sq);
+    for (size_t e = 0; e < mm; ++e) A[e] *= scale;
+    E = A;
+    for (int i = 0; i < m; ++i) E[i + (size_t)i * m] += 1.0;
+    P = A;
+    for (int k = 2; k <= 64; ++k) {
+        rmatmul(m, P.data(), A.data(), W.data());
+        const double inv = 1.0 / k;
+        for (size_t e = 0; e < mm; ++e) {
+            W[e] *= inv;
+            E[e] += W[e];
+        }
+        P.swap(W);
+        if (rnorm1(m, P.data()) < 1e-22) break;
+    }
+    for (int q = 0; q + 1 < sq; ++q) {
+        rmatmul(m, E.data(), E.data(), W.data());
+        E.swap(W);
+    }
+    if (sq > 0) {  // c = E E(:,1)
+        for (int i = 0; i < m; ++i) W[i] = 0.0;
+        for (int k = 0; k < m; ++k) {
+            const double b = E[k];
+            const double* ek = E.data() + (size_t)k * m;
+            for (int i = 0; i < m; ++i) W[i] += ek[i] * b;
+        }
+        for (int i = 0; i < m; ++i) E[i] = W[i];
+    }
+    for (int i = 0; i < m; ++i) {
+        if (!std::isfinite(E[i])) return false;  // the squarings overflowed
+        c[i] = E[i];
+    }
+    return true;
+}
+
 }  // namespace dense
 }  // namespace cal

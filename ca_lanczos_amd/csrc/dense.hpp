@@ -49,6 +49,10 @@ void matlab_rand(std::mt19937& g, int64_t count, double* out);
 // c = expm(-i dt T) e_1 for a general real m x m T (scaling and squaring with
 // a Taylor series, complex arithmetic).  False when dt T is not finite.
 bool expm_col1(int m, const double* T, int ldt, double dt, double* c_re, double* c_im);
+// c = expm(-tau (T - T(1,1) I)) e_1 for a general real m x m T (the same
+// scheme in real arithmetic; imaginary-time propagation, which uses only the
+// direction of c).  False when tau T is not finite or the result overflows.
+bool expm_real_col1(int m, const double* T, int ldt, double tau, double* c);
 
 }  // namespace dense
 }  // namespace cal

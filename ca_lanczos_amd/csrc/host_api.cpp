@@ -58,6 +58,12 @@ int cal_expm_col1(int m, const double* T, int ldt, double dt, double* c_re, doub
     return dense::expm_col1(m, T, ldt, dt, c_re, c_im) ? 0 : CAL_ERR_NUMERIC;
 }
 
+// c = expm(-tau (T - T(1,1) I)) e_1 (imaginary-time propagation)
+int cal_expm_real_col1(int m, const double* T, int ldt, double tau, double* c) {
+    if (m < 1 || m > 512 || !T || ldt < m || !c || !std::isfinite(tau)) return CAL_ERR_ARG;
+    return dense::expm_real_col1(m, T, ldt, tau, c) ? 0 : CAL_ERR_NUMERIC;
+}
+
 static std::atomic<long long> g_residency_gen{0};
 
 long long cal_residency_generation(void) { return g_residency_gen.load(std::memory_order_acquire); }

@@ -28,6 +28,15 @@
 // An absorbing mask (cal_prop_set_absorber) multiplies the state by a real
 // diagonal 0 <= M <= 1 at the end of every step, inside the combine sweep
 // (prop.hip's ABS flag), and records the squared norm it removes.
+// Imaginary time (cal_prop_set_imaginary_time) keeps the build and the combine
+// and changes the host's coefficients: c = expm(-dt (T - T(1,1) I)) e_1, real,
+// scaled to the squared norm N the mode started with -- psi <- sqrt(N) exp(-dt
+// H[psi]) psi / ||.||, whose fixed point is the ground state.  A real H has a
+// real ground state: cal_prop_begin_real runs the same host path on H itself
+// (PropState::halves = 1), the state one real vector of n rows, the combine
+// k_prop_combine_real and the density k_diag_density's REAL instantiation.
+// Every step also records [t_n, N_n, mu_n, E_n, res_n] from the first column
+// of its first build's T (cal_prop_get_energetics): no kernel, no sweep.
 // The one deliberate difference from ca_lanczos_prop.m: :78 projects with
 // doreorth = false, the blocks here apply the library's second-pass rule
 // (projectAndNormalize's 'second'), which is at least as orthogonal.
@@ -49,7 +58,8 @@
 namespace cal {
 
 struct PropState {
-    int64_t n = 0;        // rows of H (the matrix has 2n)
+    int64_t n = 0;        // rows of H (the matrix has halves * n)
+    int halves = 2;       // 2: the stacked state [Re psi; Im psi]; 1: a real state on H itself (cal_prop_begin_real)
     int s = 0, max_blocks = 0;
     bool newton = false;
     bool have_shifts = false;
@@ -60,6 +70,11 @@ struct PropState {
     double nrm2 = 0.0;           // psi'psi
     cal_prop_info info{};
     double t = 0.0;              // the accumulated time, sum of dt over the completed steps
+    // imaginary time (cal_prop_set_imaginary_time; always on with halves == 1):
+    // a step is psi <- sqrt(N0) exp(-dt H) psi / ||.||
+    bool imag = false;
+    double N0 = 0.0;             // the squared norm every step restores: the state's when the mode went on
+    std::vector<double> ehist;   // one row [t_n, N_n, mu_n, E_n, res_n] per completed step since the begin
     // observables (cal_prop_set_observables): reduced in the combine sweep
     int nw = 0, nphi = 0;
     bool energy = false;
@@ -108,6 +123,7 @@ struct PropState {
     // absorbed norm, the energy) and the nonlinear term's sum after it -- the size of h_coef's tail
     static constexpr int kRedMax = 1 + 3 * kPropMaxObs + 1 + 1 + 1;
     double* psi(const cal_ctx* c) const { return d_psi + c->A.lpad; }
+    int64_t rows() const { return halves * n; }  // of the matrix and of the state
 };
 
 namespace {
@@ -132,7 +148,7 @@ PropObs make_obs(const double* base, int64_t ldo, int nw, int nphi) {
 // 0 with a propagator open on c (and, need_matrix, the matrix it was begun on still set)
 int active_prop(cal_ctx* c, const std::string& who, bool need_matrix) {
     if (!c || !c->prop) return set_error(c, CAL_ERR_ARG, who + ": no active propagator");
-    if (need_matrix && (!c->has_A || c->A.n_local != 2 * c->prop->n))
+    if (need_matrix && (!c->has_A || c->A.n_local != c->prop->rows()))
         return set_error(c, CAL_ERR_ARG, who + ": the context's matrix changed since cal_prop_begin");
     return 0;
 }
@@ -168,15 +184,15 @@ void obs_free(PropState& P) {
 
 // V0 is still the diagonal of the context's matrix underneath what was written
 bool v0_current(const cal_ctx* c, const PropState& P) {
-    return P.d_v0 && c->has_A && c->A_gen == P.drv_gen && c->A.n_local == 2 * P.n;
+    return P.d_v0 && c->has_A && c->A_gen == P.drv_gen && c->A.n_local == P.rows();
 }
 
 // V0 + sum_k f[k] W_k (f null: V0 alone) back into the matrix V0 was taken
 // from, when that matrix is still the context's; waits for it
 int v0_write(cal_ctx* c, PropState& P, const double* f) {
     if (!v0_current(c, P)) return 0;
-    int st = f ? diag_update_dev(c, P.d_v0, P.n, 2, P.nk, P.d_drv, P.ldd, f)
-               : diag_update_dev(c, P.d_v0, P.n, 2, 0, nullptr, 0, nullptr);
+    int st = f ? diag_update_dev(c, P.d_v0, P.n, P.halves, P.nk, P.d_drv, P.ldd, f)
+               : diag_update_dev(c, P.d_v0, P.n, P.halves, 0, nullptr, 0, nullptr);
     if (hipStreamSynchronize(c->stream) != hipSuccess && st == 0) st = CAL_ERR_HIP;
     return st;
 }
@@ -258,7 +274,8 @@ void prop_free(cal_ctx* c) {
     c->prop = nullptr;
 }
 
-// psi <- Q(:, 0:m) (a + i b) and nrm2 <- psi'psi (a, b: Re / Im of nrm c, on the host)
+// psi <- Q(:, 0:m) (a + i b) and nrm2 <- psi'psi (a, b: Re / Im of nrm c, on the host);
+// a real state (halves == 1): psi <- Q(:, 0:m) a through k_prop_combine_real
 int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, const double* a, const double* b) {
     std::memcpy(P.h_coef, a, m * sizeof(double));
     std::memcpy(P.h_coef + kPropMaxCols, b, m * sizeof(double));
@@ -275,15 +292,16 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     k.obs = make_obs(P.d_obs, P.ldo, P.nw, P.nphi);
     k.mask = P.d_mask;
     k.ldm = P.ldm;
+    k.real = P.halves == 1;
     const int nb = prop_combine_blocks(P.n);
     const int nk = prop_combine_quantities(k);
-    const int nd = dot_blocks(2 * P.n);
+    const int nd = dot_blocks(P.rows());
     const size_t pe = (size_t)nk * nb;  // the energy's partials follow the combine's
     CAL_TRY(ensure_partial(c, pe + (P.energy ? (size_t)std::max(P.eparts, nd) : 0)));
     const int nred = P.red_count() + (P.nl_on() ? 1 : 0);  // the nonlinear term's sum |psi_n|^4 comes last
     CAL_TRY(ensure_red(c, (size_t)nred));
     k.partial = c->d_partial;
-    const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n + (double)P.n * (nk - 1)) * 8.0);
+    const int t = timer_begin(c, 2, ((double)P.rows() * m + (double)P.rows() + (double)P.n * (nk - 1)) * 8.0);
     const hipError_t e = launch_prop_combine(k, c->stream);
     timer_end(c, t);
     if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
@@ -299,7 +317,7 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
             CAL_HIP_OTHER(c, launch_reduce(part, P.eparts, 1, c->d_red + P.red_energy(), c->stream));
         } else {
             CAL_TRY(spmv_dev(c, P.psi(c), y, 0, 0.0, 0.0, nullptr));
-            CAL_HIP_OTHER(c, launch_dot(y, P.psi(c), 2 * P.n, part, nd, c->stream));
+            CAL_HIP_OTHER(c, launch_dot(y, P.psi(c), P.rows(), part, nd, c->stream));
             CAL_HIP_OTHER(c, launch_reduce(part, nd, 1, c->d_red + P.red_energy(), c->stream));
         }
     }
@@ -329,10 +347,11 @@ int combine_predict_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, i
     k.a = P.d_coef;
     k.b = P.d_coef + kPropMaxCols;
     k.out = P.d_psi2 + c->A.lpad;
+    k.real = P.halves == 1;
     const int nb = prop_combine_blocks(P.n);
     CAL_TRY(ensure_partial(c, (size_t)nb));
     k.partial = c->d_partial;  // the provisional state's norm is not used
-    const int t = timer_begin(c, 2, ((double)2 * P.n * m + (double)2 * P.n) * 8.0);
+    const int t = timer_begin(c, 2, ((double)P.rows() * m + (double)P.rows()) * 8.0);
     const hipError_t e = launch_prop_combine(k, c->stream);
     timer_end(c, t);
     if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
@@ -342,7 +361,7 @@ int combine_predict_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, i
 // the diagonal <- V0 + sum_k f[k] W_k + ga |psi_n|^2 (+ gb |B|^2), one launch;
 // the blocks' shares of sum |psi_n|^4 stay in d_nlpart for the step's combine
 int density_dev(cal_ctx* c, PropState& P, const double* f, double ga, const double* B, double gb) {
-    return diag_density_dev(c, P.d_v0, P.n, 2, P.nk, P.d_drv, P.ldd, f, P.psi(c), ga, B, gb, P.d_nlpart);
+    return diag_density_dev(c, P.d_v0, P.n, P.halves, P.nk, P.d_drv, P.ldd, f, P.psi(c), ga, B, gb, P.d_nlpart);
 }
 
 // the history row of the step just completed (combine_dev's transfer is in h_coef)
@@ -362,11 +381,18 @@ void record_absorbed(PropState& P) {
 
 // One Krylov build from the current state: CA blocks until max_blocks, the
 // adaptive stop or a dropped block.  *kuse blocks are usable (0: the first
-// block broke down); cre / cim: expm(-i dt T(1:ks,1:ks)) e_1 for ks = s kuse.
+// block broke down); cre / cim: expm(-i dt T(1:ks,1:ks)) e_1 for ks = s kuse,
+// and *scale = nrm: the new state is Q (scale (cre + i cim)).
+// Imaginary time: cre = expm(-dt (T - T(1,1) I)) e_1 (real), cim = 0, *scale =
+// sqrt(N0) / ||cre||_2 (the sum of squares in ascending order) -- the new state
+// has the squared norm N0 -- and the residual is |dt b(k) c(ks)| *scale.
+// en non-null: en[0] = T(1,1) = <psi|H|psi>/<psi|psi> and en[1] = ||T(2:ks,1)||_2,
+// the eigen-residual of the start state (Q(:,1) is psi / ||psi||).
 int krylov(cal_ctx* c, PropState& P, double dt, double tol, int adaptive, int* kuse, std::vector<double>& cre,
-           std::vector<double>& cim, double* resid) {
+           std::vector<double>& cim, double* resid, double* scale, double* en) {
     const int s = P.s;
     const double nrm = std::sqrt(P.nrm2);
+    *scale = nrm;
     LanczosBegin in;
     in.r_dev = P.psi(c);
     in.rr = P.nrm2;
@@ -401,14 +427,33 @@ int krylov(cal_ctx* c, PropState& P, double dt, double tol, int adaptive, int* k
         P.info.rank_deficient += v.n_rank_deficient - rd0;
         const int ks = k * s;
         double r = std::numeric_limits<double>::quiet_NaN();
-        if (dense::expm_col1(ks, v.T, v.ldt, dt, tre.data(), tim.data()))
+        double sc = nrm;
+        if (P.imag) {
+            if (dense::expm_real_col1(ks, v.T, v.ldt, dt, tre.data())) {
+                double cc = 0.0;
+                for (int j = 0; j < ks; ++j) {
+                    cc = cc + tre[j] * tre[j];
+                    tim[j] = 0.0;
+                }
+                sc = std::sqrt(P.N0) / std::sqrt(cc);
+                r = std::fabs(dt * v.b[k - 1] * tre[ks - 1]) * sc;
+            }
+        } else if (dense::expm_col1(ks, v.T, v.ldt, dt, tre.data(), tim.data())) {
             r = std::fabs(dt * v.b[k - 1] * nrm) * std::hypot(tre[ks - 1], tim[ks - 1]);  // :123
+        }
         if (!std::isfinite(r)) {  // a non-finite T: the block is dropped like a breakdown
             P.info.breakdowns++;
             break;
         }
         *kuse = k;
         *resid = r;
+        *scale = sc;
+        if (en) {
+            double rr = 0.0;
+            for (int i = 1; i < ks; ++i) rr = rr + v.T[i] * v.T[i];
+            en[0] = v.T[0];
+            en[1] = std::sqrt(rr);
+        }
         cre.assign(tre.begin(), tre.begin() + ks);
         cim.assign(tim.begin(), tim.begin() + ks);
         if (adaptive && r < tol && ks >= 3) break;  // :124
@@ -416,14 +461,35 @@ int krylov(cal_ctx* c, PropState& P, double dt, double tol, int adaptive, int* k
     return 0;
 }
 
-int check_prop_args(cal_ctx* c, int64_t n, int s, int max_blocks, const char* basis, bool* newton) {
+int check_prop_args(cal_ctx* c, int64_t n, int halves, int s, int max_blocks, const char* basis, bool* newton) {
     if (!c) return CAL_ERR_ARG;
     hipSetDevice(c->device);
     if (!c->has_A) return set_error(c, CAL_ERR_NOMATRIX, "no matrix set on the context");
-    if (c->comm && c->comm->nranks > 1)
-        return set_error(c, CAL_ERR_UNSUPPORTED, "time propagation runs on one rank");
-    if (n < 1 || c->A.n_local != 2 * n)
-        return set_error(c, CAL_ERR_ARG, "cal_prop: the matrix must have 2n rows (cal_set_matrix_csr_stacked)");
+    if (halves == 1) {
+        // the real-state path runs on H itself: what only the stacked propagator takes is refused
+        if (c->comm && c->comm->nranks > 1)
+            return set_error(c, CAL_ERR_UNSUPPORTED, "cal_prop_begin_real: the real-state path runs on one rank, as "
+                                                     "the stacked propagator (cal_prop_begin) does");
+        if (c->A.herm)
+            return set_error(c, CAL_ERR_UNSUPPORTED, "cal_prop_begin_real: a complex Hermitian matrix has a complex "
+                                                     "ground state; use the stacked propagator (cal_prop_begin) "
+                                                     "with cal_prop_set_imaginary_time");
+        if (c->A.shared)
+            return set_error(c, CAL_ERR_UNSUPPORTED, "cal_prop_begin_real: a \"shared\" matrix is blkdiag(H, H); set H "
+                                                     "itself (cal_set_matrix_csr) or use the stacked propagator "
+                                                     "(cal_prop_begin) with cal_prop_set_imaginary_time");
+        if (n >= 1 && c->A.n_local == 2 * n)
+            return set_error(c, CAL_ERR_UNSUPPORTED, "cal_prop_begin_real: the matrix has 2n rows, a stacked matrix; "
+                                                     "set H itself (cal_set_matrix_csr) or use the stacked "
+                                                     "propagator (cal_prop_begin) with cal_prop_set_imaginary_time");
+        if (n < 1 || c->A.n_local != n)
+            return set_error(c, CAL_ERR_ARG, "cal_prop_begin_real: the matrix must have n rows (cal_set_matrix_csr)");
+    } else {
+        if (c->comm && c->comm->nranks > 1)
+            return set_error(c, CAL_ERR_UNSUPPORTED, "time propagation runs on one rank");
+        if (n < 1 || c->A.n_local != 2 * n)
+            return set_error(c, CAL_ERR_ARG, "cal_prop: the matrix must have 2n rows (cal_set_matrix_csr_stacked)");
+    }
     if (s < 1 || s > 31 || max_blocks < 1 || (int64_t)s * max_blocks > kPropMaxCols)
         return set_error(c, CAL_ERR_ARG, "cal_prop: need 1 <= s <= 31 and s*max_blocks <= 512");
     std::string b = basis ? basis : "";
@@ -498,6 +564,53 @@ int combine_host(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_
     if (norm2) *norm2 = red[0];
     for (int q = 0; q < nq; ++q) sums[q] = red[1 + q];
     if (mask && absorbed) *absorbed = red[1 + nq];
+    return 0;
+}
+
+// The real state's sweep on host data, behind cal_prop_combine_real / _ld.  Q
+// has the host leading dimension ldq >= n.  ldq == n: the device copy takes
+// the library's own padded leading dimension (a multiple of 64: the 16-byte
+// path).  ldq > n: the copy keeps ldq, so an odd ldq runs the 8-byte path.
+// d_scratch holds [out (ldo) | W (ldo x nw) | a (m rounded up to even) | Q
+// (ld x m)], ldo a multiple of 64: every origin is 16-byte aligned.
+int combine_real_host(cal_ctx* c, int64_t n, int m, const double* Q, int64_t ldq, const double* a, int nw,
+                      const double* W, double* out, double* norm2, double* sums) {
+    const int64_t ldo = pad64(n), ld = ldq == n ? ldo : ldq;
+    const size_t ma = (size_t)m + (m & 1);
+    CAL_TRY(ensure_scratch(c, (size_t)ldo * (1 + nw) + ma + (size_t)ld * m));
+    double* dout = c->d_scratch;
+    double* dobs = dout + ldo;
+    double* dco = dobs + (size_t)ldo * nw;
+    double* dq = dco + ma;
+    PropCombine k;
+    k.Q = dq;
+    k.ld = ld;
+    k.n = n;
+    k.m = m;
+    k.a = dco;
+    k.out = dout;
+    k.obs = make_obs(dobs, ldo, nw, 0);
+    k.real = true;
+    const int nb = prop_combine_blocks(n);
+    const int nk = prop_combine_quantities(k);
+    CAL_TRY(ensure_partial(c, (size_t)nk * nb));
+    CAL_TRY(ensure_red(c, (size_t)nk));
+    k.partial = c->d_partial;
+    CAL_HIP(c, hipMemcpy2DAsync(dq, ld * sizeof(double), Q, ldq * sizeof(double), n * sizeof(double), m,
+                                hipMemcpyHostToDevice, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(dco, a, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CAL_TRY(upload_cols(c, dobs, ldo, W, n, nw));
+    const int t = timer_begin(c, 2, ((double)n * m + (double)n + (double)n * nw) * 8.0);
+    const hipError_t e = launch_prop_combine(k, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
+    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, nk, c->d_red, c->stream));
+    CAL_HIP(c, hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    double red[1 + kPropMaxObs] = {0.0};
+    CAL_HIP(c, hipMemcpyAsync(red, c->d_red, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CAL_HIP(c, hipStreamSynchronize(c->stream));
+    if (norm2) *norm2 = red[0];
+    for (int q = 0; q < nw; ++q) sums[q] = red[1 + q];
     return 0;
 }
 
@@ -641,6 +754,23 @@ int cal_prop_combine_obs(cal_ctx* c, int64_t n, int m, const double* Q, const do
                         sums);
 }
 
+int cal_prop_combine_real_ld(cal_ctx* c, int64_t n, int m, const double* Q, int64_t ldq, const double* a, int nw,
+                             const double* W, double* out, double* norm2, double* sums) {
+    if (!c) return CAL_ERR_ARG;
+    hipSetDevice(c->device);
+    if (n < 1 || m < 1 || m > kPropMaxCols || !Q || ldq < n || !a || !out)
+        return set_error(c, CAL_ERR_ARG,
+                         "cal_prop_combine_real: need n >= 1, 1 <= m <= 512, ldq >= n and non-null arrays");
+    if (nw < 0 || nw > kPropMaxObs || (nw > 0 && (!W || !sums)))
+        return set_error(c, CAL_ERR_ARG, "cal_prop_combine_real: need 0 <= nw <= 4 with W and sums");
+    return combine_real_host(c, n, m, Q, ldq, a, nw, W, out, norm2, sums);
+}
+
+int cal_prop_combine_real(cal_ctx* c, int64_t n, int m, const double* Q, const double* a, int nw, const double* W,
+                          double* out, double* norm2, double* sums) {
+    return cal_prop_combine_real_ld(c, n, m, Q, n, a, nw, W, out, norm2, sums);
+}
+
 int cal_prop_set_observables(cal_ctx* c, int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
                              int energy) {
     CAL_TRY(active_prop(c, "cal_prop_set_observables", true));
@@ -648,6 +778,10 @@ int cal_prop_set_observables(cal_ctx* c, int nw, const double* W, int nphi, cons
     PropState& P = *c->prop;
     if (!obs_counts_ok(nw, W, nphi, phi_re))
         return set_error(c, CAL_ERR_ARG, "cal_prop_set_observables: need 0 <= nw, nphi <= 4 with their arrays");
+    if (P.halves == 1 && nphi > 0)
+        return set_error(c, CAL_ERR_UNSUPPORTED, "cal_prop_set_observables: a real-state propagator "
+                                                 "(cal_prop_begin_real) takes W and energy only; reference states "
+                                                 "need the stacked propagator (cal_prop_begin)");
     CAL_HIP(c, hipStreamSynchronize(c->stream));
     obs_free(P);
     const int nq = nw + 2 * nphi;
@@ -707,6 +841,10 @@ int cal_prop_set_absorber(cal_ctx* c, const double* mask) {
     CAL_TRY(active_prop(c, "cal_prop_set_absorber", false));
     hipSetDevice(c->device);
     PropState& P = *c->prop;
+    if (P.halves == 1)
+        return set_error(c, CAL_ERR_UNSUPPORTED, "cal_prop_set_absorber: a real-state propagator "
+                                                 "(cal_prop_begin_real) takes no absorber; use the stacked "
+                                                 "propagator (cal_prop_begin)");
     if (mask && !mask_ok(mask, P.n))
         return set_error(c, CAL_ERR_ARG, "cal_prop_set_absorber: the mask must be finite and within [0, 1]");
     CAL_HIP(c, hipStreamSynchronize(c->stream));
@@ -741,16 +879,18 @@ int cal_prop_get_absorbed(cal_ctx* c, int64_t first, int64_t count, double* out,
     return 0;
 }
 
-static int prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* psi_im, int s, int max_blocks,
-                      const char* basis, const double* eigest, int neig) {
+// halves = 1: the real-state path (psi_im unused)
+static int prop_begin(cal_ctx* c, int64_t n, int halves, const double* psi_re, const double* psi_im, int s,
+                      int max_blocks, const char* basis, const double* eigest, int neig) {
     bool newton = false;
-    CAL_TRY(check_prop_args(c, n, s, max_blocks, basis, &newton));
+    CAL_TRY(check_prop_args(c, n, halves, s, max_blocks, basis, &newton));
     if (!psi_re || neig < 0 || (neig > 0 && !eigest))
         return set_error(c, CAL_ERR_ARG, "cal_prop_begin: need psi_re (and eigest when neig > 0)");
     prop_free(c);
     PropState* P = new PropState();
     c->prop = P;
     P->n = n;
+    P->halves = halves;
     P->s = s;
     P->max_blocks = max_blocks;
     P->newton = newton;
@@ -777,13 +917,13 @@ static int prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double*
     std::memset(P->h_coef, 0, (2 * kPropMaxCols + PropState::kRedMax) * sizeof(double));
     CAL_HIP(c, hipMemsetAsync(P->d_psi, 0, ld * sizeof(double), c->stream));
     CAL_HIP(c, hipMemcpyAsync(P->psi(c), psi_re, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (psi_im)
+    if (psi_im && halves == 2)
         CAL_HIP(c, hipMemcpyAsync(P->psi(c) + n, psi_im, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     // the first norm: one sweep; every later one comes out of the combine
-    const int nb = dot_blocks(2 * n);
+    const int nb = dot_blocks(P->rows());
     CAL_TRY(ensure_partial(c, nb));
     CAL_TRY(ensure_red(c, 1));
-    CAL_HIP_OTHER(c, launch_dot(P->psi(c), P->psi(c), 2 * n, c->d_partial, nb, c->stream));
+    CAL_HIP_OTHER(c, launch_dot(P->psi(c), P->psi(c), P->rows(), c->d_partial, nb, c->stream));
     CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, 1, c->d_red, c->stream));
     CAL_HIP(c, hipMemcpyAsync(P->h_coef + 2 * kPropMaxCols, c->d_red, sizeof(double), hipMemcpyDeviceToHost,
                               c->stream));
@@ -792,14 +932,52 @@ static int prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double*
     if (!(P->nrm2 > 0.0) || !std::isfinite(P->nrm2))
         return set_error(c, CAL_ERR_ARG, "cal_prop_begin: the start state must be finite and non-zero");
     P->info.norm = std::sqrt(P->nrm2);
+    if (halves == 1) {  // imaginary time from the start: N = psi'psi
+        P->imag = true;
+        P->N0 = P->nrm2;
+    }
     return 0;
 }
 
 int cal_prop_begin(cal_ctx* c, int64_t n, const double* psi_re, const double* psi_im, int s, int max_blocks,
                    const char* basis, const double* eigest, int neig) {
-    const int st = prop_begin(c, n, psi_re, psi_im, s, max_blocks, basis, eigest, neig);
+    const int st = prop_begin(c, n, 2, psi_re, psi_im, s, max_blocks, basis, eigest, neig);
     if (st < 0 && c) prop_free(c);  // no half-built propagator is left behind
     return st;
+}
+
+int cal_prop_begin_real(cal_ctx* c, int64_t n, const double* psi, int s, int max_blocks, const char* basis,
+                        const double* eigest, int neig) {
+    // a refusal of the matrix leaves an open propagator as it was (prop_begin frees it only after the checks)
+    const bool had = c && c->prop;
+    const int st = prop_begin(c, n, 1, psi, nullptr, s, max_blocks, basis, eigest, neig);
+    if (st < 0 && c && c->prop && !(had && st == CAL_ERR_UNSUPPORTED)) prop_free(c);
+    return st;
+}
+
+int cal_prop_set_imaginary_time(cal_ctx* c, int on) {
+    CAL_TRY(active_prop(c, "cal_prop_set_imaginary_time", false));
+    PropState& P = *c->prop;
+    if (!on && P.halves == 1)
+        return set_error(c, CAL_ERR_UNSUPPORTED, "cal_prop_set_imaginary_time: a real-state propagator "
+                                                 "(cal_prop_begin_real) steps in imaginary time only; real time "
+                                                 "needs the stacked propagator (cal_prop_begin)");
+    if (on && !P.imag) P.N0 = P.nrm2;  // the squared norm every later step restores
+    P.imag = on != 0;
+    return 0;
+}
+
+int cal_prop_get_energetics(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows) {
+    if (!c) return CAL_ERR_ARG;
+    CAL_TRY(active_prop(c, "cal_prop_get_energetics", false));
+    const PropState& P = *c->prop;
+    const int64_t nr = (int64_t)(P.ehist.size() / 5);
+    if (nrows) *nrows = nr;
+    if (!out) return 0;
+    if (first < 0 || count < 0 || first + count > nr)
+        return set_error(c, CAL_ERR_ARG, "cal_prop_get_energetics: rows [first, first + count) out of range");
+    std::memcpy(out, P.ehist.data() + (size_t)first * 5, (size_t)count * 5 * sizeof(double));
+    return 0;
 }
 
 // nsteps time steps; f non-null: before step `it` the diagonal is set to
@@ -835,9 +1013,10 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
     for (int it = 0; it < nsteps; ++it) {
         if (f)
             for (int k = 0; k < P.nk; ++k) P.f_last[k] = f[(size_t)it * ldf + k];
-        const double nrm = std::sqrt(P.nrm2);
+        const double nrm2_n = P.nrm2;  // psi_n's: the energetics row's N_n
         int kuse = 0;
-        double resid = 0.0;
+        double resid = 0.0, scale = 0.0;
+        double en[2] = {0.0, 0.0};  // mu_n and res_n, from the step's first build
         if (P.nl_on()) {
             // the drive and the density of psi_n in one launch; "midpoint" then
             // predicts psi* into d_psi2 (psi_n and its norm stay where they
@@ -845,7 +1024,7 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
             status = density_dev(c, P, P.f_last, P.g, nullptr, 0.0);
             if (status < 0) break;
             if (P.nl_mid) {
-                status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid);
+                status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid, &scale, en);
                 if (status < 0) break;
                 if (kuse == 0) {  // the state is unchanged
                     status = set_error(c, CAL_WARN_BREAKDOWN, w + ": the predictor's first CA block broke down");
@@ -853,8 +1032,8 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
                 }
                 const int kp = kuse * P.s;
                 for (int j = 0; j < kp; ++j) {
-                    cre[j] = nrm * cre[j];
-                    cim[j] = nrm * cim[j];
+                    cre[j] = scale * cre[j];
+                    cim[j] = scale * cim[j];
                 }
                 const LanczosView vp = lanczos_view(c);
                 status = combine_predict_dev(c, P, vp.Q, vp.ld, kp, cre.data(), cim.data());
@@ -864,19 +1043,20 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
                 kuse = 0;
             }
         } else if (f) {
-            status = diag_update_dev(c, P.d_v0, P.n, 2, P.nk, P.d_drv, P.ldd, f + (size_t)it * ldf);
+            status = diag_update_dev(c, P.d_v0, P.n, P.halves, P.nk, P.d_drv, P.ldd, f + (size_t)it * ldf);
             if (status < 0) break;
         }
-        status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid);
+        status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid, &scale,
+                        P.nl_on() && P.nl_mid ? nullptr : en);
         if (status < 0) break;
         if (kuse == 0) {  // the state is unchanged
             status = set_error(c, CAL_WARN_BREAKDOWN, w + ": the first CA block broke down");
             break;
         }
         const int ks = kuse * P.s;
-        for (int j = 0; j < ks; ++j) {  // nrm * c
-            cre[j] = nrm * cre[j];
-            cim[j] = nrm * cim[j];
+        for (int j = 0; j < ks; ++j) {  // nrm * c (imaginary time: sqrt(N0) c / ||c||)
+            cre[j] = scale * cre[j];
+            cim[j] = scale * cim[j];
         }
         const LanczosView v = lanczos_view(c);
         status = combine_dev(c, P, v.Q, v.ld, ks, cre.data(), cim.data());
@@ -884,6 +1064,12 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
         if (P.nl_on()) {  // [t_n, sum |psi_n|^4]: the state the step started from
             P.nhist.push_back(P.t);
             P.nhist.push_back(P.h_coef[2 * kPropMaxCols + P.red_count()]);
+        }
+        {  // [t_n, N_n, mu_n, E_n, res_n]: E_n = N_n mu_n - (g/2) sum |psi_n|^4
+            double E = nrm2_n * en[0];
+            if (P.nl_on()) E = E - 0.5 * P.g * P.h_coef[2 * kPropMaxCols + P.red_count()];
+            const double row[5] = {P.t, nrm2_n, en[0], E, en[1]};
+            P.ehist.insert(P.ehist.end(), row, row + 5);
         }
         P.t += dt;
         if (P.obs_on()) record_row(P);
@@ -1018,7 +1204,8 @@ int cal_prop_get(cal_ctx* c, double* psi_re, double* psi_im, cal_prop_info* info
     hipSetDevice(c->device);
     PropState& P = *c->prop;
     if (psi_re) CAL_HIP(c, hipMemcpyAsync(psi_re, P.psi(c), P.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (psi_im)
+    if (psi_im && P.halves == 1) std::memset(psi_im, 0, P.n * sizeof(double));  // a real state
+    if (psi_im && P.halves == 2)
         CAL_HIP(c, hipMemcpyAsync(psi_im, P.psi(c) + P.n, P.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (psi_re || psi_im) CAL_HIP(c, hipStreamSynchronize(c->stream));
     if (info) {
@@ -1049,7 +1236,8 @@ int cal_ca_lanczos_prop(cal_ctx* c, int64_t n, const double* r_re, const double*
     std::vector<double> cre, cim;
     int kuse = 0;
     double resid = 0.0;
-    int status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid);
+    double scale = 0.0;
+    int status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid, &scale, nullptr);
     if (status >= 0 && kuse == 0)
         status = set_error(c, CAL_WARN_BREAKDOWN, "cal_ca_lanczos_prop: the first CA block broke down");
     if (status == 0) {

@@ -313,6 +313,107 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
     }
 }
 
+// k_prop_combine_real: the combine of a real state (cal_prop_begin_real; an
+// imaginary-time step keeps a real state real), out[i] = sum_j Q[i,j] a_j for
+// i in [0, n) -- k_prop_combine without the lower half: the same rows per lane
+// and per block, a staged in LDS, 16-byte accesses when V (the origins of Q and
+// out 16-byte aligned, ld even), 8-byte ones otherwise and for the last row of
+// an odd n.  Per row: t = +0.0; j ascending: t = t + x*a_j; then, a lane's rows
+// in row order, nrm = nrm + t*t and with OBS, for k < nw,
+//   d = t*t;  accW[k] = accW[k] + w*d
+// reduced as k_prop_combine reduces (wave tree, the four waves in order,
+// quantity q's block share at partial[q * gridDim.x + block]: q = 0 the squared
+// norm, 1 + k <W_k>).  (n m + n + n nw) 8 bytes; vector stores only.
+template <bool V, bool OBS>
+__global__ __launch_bounds__(kPropThreads) void k_prop_combine_real(const double* __restrict__ Q, int64_t ld,
+                                                                    int64_t n, int m, const double* __restrict__ a,
+                                                                    double* __restrict__ out,
+                                                                    double* __restrict__ partial,
+                                                                    PropObsArg<OBS, false> obs) {
+    __shared__ double sa[kPropMaxCols];
+    __shared__ double ws[kPropThreads / 64];
+    double accw[kPropMaxObs];
+    if constexpr (OBS) {
+#pragma unroll
+        for (int k = 0; k < kPropMaxObs; ++k) accw[k] = 0.0;
+    }
+    for (int j = threadIdx.x; j < m; j += kPropThreads) sa[j] = a[j];
+    __syncthreads();
+
+    const int64_t base = (int64_t)blockIdx.x * kPropBlockRows;
+    double nrm = 0.0;
+#pragma unroll
+    for (int p = 0; p < kPropPairs; ++p) {
+        const int64_t r = base + 2 * ((int64_t)p * kPropThreads + threadIdx.x);
+        if (r + 1 < n) {
+            const double* q = Q + r;
+            double t0 = 0.0, t1 = 0.0;
+#pragma unroll 4
+            for (int j = 0; j < m; ++j) {
+                double x0, x1;
+                load2<V>(q, x0, x1);
+                q += ld;
+                const double aj = sa[j];
+                t0 = t0 + x0 * aj;
+                t1 = t1 + x1 * aj;
+            }
+            store2<V>(out + r, t0, t1);
+            nrm = nrm + t0 * t0;
+            nrm = nrm + t1 * t1;
+            if constexpr (OBS) {
+#pragma unroll
+                for (int k = 0; k < kPropMaxObs; ++k)
+                    if (k < obs.o.nw) {
+                        double w0, w1;
+                        load2<true>(obs.o.W + k * obs.o.ld + r, w0, w1);
+                        double d = t0 * t0;
+                        accw[k] = accw[k] + w0 * d;
+                        d = t1 * t1;
+                        accw[k] = accw[k] + w1 * d;
+                    }
+            }
+        } else if (r < n) {  // the last row of an odd n
+            const double* q = Q + r;
+            double t0 = 0.0;
+            for (int j = 0; j < m; ++j) {
+                const double x0 = *q;
+                q += ld;
+                t0 = t0 + x0 * sa[j];
+            }
+            out[r] = t0;
+            nrm = nrm + t0 * t0;
+            if constexpr (OBS) {
+#pragma unroll
+                for (int k = 0; k < kPropMaxObs; ++k)
+                    if (k < obs.o.nw) {
+                        const double d = t0 * t0;
+                        accw[k] = accw[k] + obs.o.W[k * obs.o.ld + r] * d;
+                    }
+            }
+        }
+    }
+    nrm = prop_wave_sum(nrm);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) ws[wave] = nrm;
+    if constexpr (OBS) {
+        double(*wo)[kPropThreads / 64] = obs_wave_sums();
+#pragma unroll
+        for (int k = 0; k < kPropMaxObs; ++k)
+            if (k < obs.o.nw) {
+                const double v = prop_wave_sum(accw[k]);
+                if (lane == 0) wo[k][wave] = v;
+            }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+    if constexpr (OBS) {  // thread q writes quantity q of this block
+        double(*wo)[kPropThreads / 64] = obs_wave_sums();
+        const int q = (int)threadIdx.x - 1;
+        if (q >= 0 && q < obs.o.nw)
+            partial[(int64_t)(q + 1) * gridDim.x + blockIdx.x] = ((wo[q][0] + wo[q][1]) + wo[q][2]) + wo[q][3];
+    }
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -352,10 +453,27 @@ static bool obs_arg_ok(const PropObs& o, int64_t n) {
     return true;
 }
 
+// the real state's sweep: one half, V from the alignment of Q and out
+template <bool OBS>
+static hipError_t launch_combine_real(const PropCombine& p, PropObsArg<OBS, false> obs, hipStream_t st) {
+    const dim3 grid((unsigned)prop_combine_blocks(p.n)), block(kPropThreads);
+    auto launch = [&](auto k) {
+        hipLaunchKernelGGL(k, grid, block, 0, st, p.Q, p.ld, p.n, p.m, p.a, p.out, p.partial, obs);
+    };
+    if ((p.ld & 1) == 0 && aligned16(p.Q) && aligned16(p.out)) launch(k_prop_combine_real<true, OBS>);
+    else launch(k_prop_combine_real<false, OBS>);
+    return hipGetLastError();
+}
+
 hipError_t launch_prop_combine(const PropCombine& p, hipStream_t st) {
-    if (p.n < 1 || p.m < 1 || p.m > kPropMaxCols || p.ld < 2 * p.n) return hipErrorInvalidValue;
+    if (p.n < 1 || p.m < 1 || p.m > kPropMaxCols || p.ld < (p.real ? 1 : 2) * p.n) return hipErrorInvalidValue;
     if (p.n > ((int64_t)1 << 40)) return hipErrorInvalidValue;
     if (!obs_arg_ok(p.obs, p.n)) return hipErrorInvalidValue;
+    if (p.real) {  // no reference states and no mask on a real state
+        if (p.obs.np > 0 || p.mask) return hipErrorInvalidValue;
+        if (p.obs.nw > 0) return launch_combine_real(p, PropObsArg<true, false>{p.obs}, st);
+        return launch_combine_real(p, PropObsArg<false, false>{}, st);
+    }
     // the mask's 16-byte loads: the rules of the observables' columns
     if (p.mask && (!aligned16(p.mask) || p.ldm < p.n || (p.ldm & 1) != 0)) return hipErrorInvalidValue;
     const bool obs = p.obs.nw + p.obs.np > 0;
@@ -448,22 +566,30 @@ __global__ __launch_bounds__(kDiagThreads) void k_diag_drive(DiagDrive a) {
 //   p = ga*ra;  d = d + p;  [p = gb*rb;  d = d + p]  the drive's stores
 // and the lane's q = ra*ra (0 past row n) summed as everything else here:
 // wave tree, the four waves in order, one partial per block.  No lane leaves
-// before the barrier.
-template <bool SPLIT, bool TWO>
+// before the barrier.  REAL: the states are real vectors of n rows
+// (cal_prop_begin_real), there is no lower half to load -- ra = ua*ua, rb =
+// ub*ub -- and halves is 1; everything else is the same.
+template <bool SPLIT, bool TWO, bool REAL = false>
 __global__ __launch_bounds__(kDiagThreads) void k_diag_density(DiagDensity a) {
     __shared__ double ws[kDiagThreads / 64];
     const int64_t n = a.d.n;
     const int64_t i = (int64_t)blockIdx.x * kDiagThreads + threadIdx.x;
     double acc = 0.0;
     if (i < n) {
-        const double ua = a.A[i], va = a.A[n + i];
+        const double ua = a.A[i];
         double ra = ua * ua;
-        ra = ra + va * va;
+        if constexpr (!REAL) {
+            const double va = a.A[n + i];
+            ra = ra + va * va;
+        }
         double rb = 0.0;
         if (TWO) {
-            const double ub = a.B[i], vb = a.B[n + i];
+            const double ub = a.B[i];
             rb = ub * ub;
-            rb = rb + vb * vb;
+            if constexpr (!REAL) {
+                const double vb = a.B[n + i];
+                rb = rb + vb * vb;
+            }
         }
         double d = a.d.V0[i];
 #pragma unroll
@@ -533,7 +659,16 @@ hipError_t launch_diag_density(const DiagDensity& a, hipStream_t st) {
     if (!a.A || !a.partial) return hipErrorInvalidValue;
     const dim3 grid((unsigned)diag_density_blocks(d.n)), block(kDiagThreads);
     auto launch = [&](auto k) { hipLaunchKernelGGL(k, grid, block, 0, st, a); };
-    if (d.ds_diag) {
+    if (a.real) {
+        if (d.halves != 1) return hipErrorInvalidValue;
+        if (d.ds_diag) {
+            if (a.B) launch(k_diag_density<true, true, true>);
+            else launch(k_diag_density<true, false, true>);
+        } else {
+            if (a.B) launch(k_diag_density<false, true, true>);
+            else launch(k_diag_density<false, false, true>);
+        }
+    } else if (d.ds_diag) {
         if (a.B) launch(k_diag_density<true, true>);
         else launch(k_diag_density<true, false>);
     } else {

@@ -899,6 +899,7 @@ int diag_density_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, in
     if (halves < 1 || halves > 2 || n < 1 || n * halves != A.n_local || nk < 0 || nk > kDriveMaxOps || !V0_dev ||
         (nk > 0 && (!W_dev || !f || ldw < n)) || !A_dev || !partial)
         return set_error(c, CAL_ERR_ARG, "diag_density_dev: bad arguments");
+    const bool real = halves == 1;  // the states are real vectors of n rows
     if (A.shared) {  // both halves read one slot: it is written once, on H's rows
         if (halves != 2)
             return set_error(c, CAL_ERR_ARG, "diag_density_dev: a shared matrix takes both halves at once");
@@ -920,9 +921,10 @@ int diag_density_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, in
     a.ga = ga;
     a.gb = B_dev ? gb : 0.0;
     a.partial = partial;
-    // the drive's bytes and the 2n doubles of each state in; one partial per block out
+    a.real = real;
+    // the drive's bytes and the 2n (real: n) doubles of each state in; one partial per block out
     const double bytes = (double)n * (8.0 * (1 + nk) + 4.0 * halves) + (double)n * halves * (A.use_dsplit ? 16.0 : 8.0) +
-                         (double)n * 16.0 * (B_dev ? 2 : 1) + 8.0 * diag_density_blocks(n);
+                         (double)n * (real ? 8.0 : 16.0) * (B_dev ? 2 : 1) + 8.0 * diag_density_blocks(n);
     const int t = timer_begin(c, 7, bytes);  // the drive's kind: the one launch that rewrites the diagonal
     const hipError_t e = launch_diag_density(a, c->stream);
     timer_end(c, t);

@@ -546,10 +546,10 @@ int cal_prop_refresh_shifts(cal_ctx* ctx);
  * CAL_ERR_ARG for a NULL context, no active propagator, a non-finite g or a
  * density other than the two; CAL_ERR_UNSUPPORTED as cal_prop_set_drive, with
  * the matrix untouched.  Setting the term clears its history.
- * Not built: the conserved Gross-Pitaevskii energy as an observable (the
- * energy observable stays <psi'|H|psi'> with the H stored in the matrix:
- * under "midpoint" H0 + drive + g (|psi_n|^2 + |psi*|^2)/2), and more than
- * second order in the nonlinear part (a "cf4" drive's sub-steps are
+ * The conserved Gross-Pitaevskii energy is a column of cal_prop_get_energetics
+ * (the energy observable stays <psi'|H|psi'> with the H stored in the matrix:
+ * under "midpoint" H0 + drive + g (|psi_n|^2 + |psi*|^2)/2).  Not built: more
+ * than second order in the nonlinear part (a "cf4" drive's sub-steps are
  * nonlinear steps each). */
 int cal_prop_set_nonlinear(cal_ctx* ctx, double g, const char* density);
 /* One row [t_n, sum_i |psi_n,i|^4] per completed step since the term was set,
@@ -560,6 +560,69 @@ int cal_prop_set_nonlinear(cal_ctx* ctx, double g, const char* density);
  * step's squared norm, in the same transfer.  out == NULL: only *nrows.
  * Copies rows [first, first+count), two doubles each. */
 int cal_prop_get_nonlinear(cal_ctx* ctx, int64_t first, int64_t count, double* out, int64_t* nrows);
+
+/* ---- imaginary time: psi <- sqrt(N) exp(-tau H[psi]) psi / ||.||, ground states ---- */
+/* on != 0: from now on cal_prop_step and cal_prop_step_driven take dt as the
+ * imaginary-time step tau.  The Krylov build is unchanged; after block k
+ *   c = expm(-tau (T(1:ks,1:ks) - T(1,1) I)) e_1           (cal_expm_real_col1)
+ *   cc = sum_j c_j^2 (j ascending);  sc = sqrt(N) / sqrt(cc)
+ * and the coefficients handed to the combine sweep are a = sc*c, b = 0: the
+ * kernel is the real-time one, and the new state has the squared norm N up to
+ * Q's loss of orthogonality (the measured squared norm still normalises the
+ * next start vector).  N is the state's squared norm when the mode went on.
+ * The adaptive / reported residual is |tau b(k) c(ks)| sc.  Under
+ * cal_prop_set_nonlinear "frozen" and "midpoint" keep their meaning (the
+ * predictor's coefficients are normalised the same way); observables, energy,
+ * absorber and drive work as in real time, on every matrix cal_prop_begin
+ * takes; t accumulates tau.  on = 0 returns to real time
+ * (CAL_ERR_UNSUPPORTED on a real-state propagator).  CAL_ERR_ARG without an
+ * active propagator. */
+int cal_prop_set_imaginary_time(cal_ctx* ctx, int on);
+/* One row [t_n, N_n, mu_n, E_n, res_n] per completed step since
+ * cal_prop_begin, in real and in imaginary time, of the state psi_n the step
+ * started from (N_n its squared norm).  Q(:,1) = psi_n/||psi_n||, so with T
+ * of the step's first Krylov build (under "midpoint" the predictor's, whose
+ * matrix H0 + drive + g |psi_n|^2 is self-consistent for psi_n):
+ *   mu_n  = T(1,1)              = <psi_n|H[psi_n]|psi_n>/N_n   (the chemical potential)
+ *   res_n = ||T(2:ks,1)||_2     = ||H[psi_n] psi_n - mu_n psi_n|| / sqrt(N_n)
+ *   E_n   = N_n mu_n - (g/2) sum_i |psi_n,i|^4                 (N_n mu_n without a nonlinear term)
+ * no kernel and no sweep: the sum is the one cal_prop_get_nonlinear records.
+ * In real time E_n is the conserved Gross-Pitaevskii energy, at that step's
+ * drive amplitudes.  A step that ends in CAL_WARN_BREAKDOWN records no row.
+ * out == NULL: only *nrows.  Copies rows [first, first+count), five doubles each. */
+int cal_prop_get_energetics(cal_ctx* ctx, int64_t first, int64_t count, double* out, int64_t* nrows);
+/* The real-state propagator: imaginary time on H itself.  The ground state of
+ * a real symmetric H is real, with or without g |psi|^2, so the state is one
+ * real device vector of n rows and the context's matrix the n x n H
+ * (cal_set_matrix_csr / _csc, in whatever SpMV format the upload chose): half
+ * the rows and half the bytes of every SpMV and sweep of the stacked route.
+ * Imaginary time is on from the start (N = psi'psi) and cannot be switched
+ * off.  cal_prop_step, _step_driven, _set_drive, _set_nonlinear (both
+ * densities; the density kernel's REAL instantiation: ra = ua*ua, rb = ub*ub,
+ * the rest of its chain unchanged), _get_nonlinear, _get_energetics,
+ * _refresh_shifts, _get (psi_im, when given, is filled with zeros) and _end
+ * work as on the stacked propagator; cal_prop_set_observables takes W and
+ * energy (nphi > 0: CAL_ERR_UNSUPPORTED), cal_prop_set_absorber is refused.
+ * CAL_ERR_UNSUPPORTED, naming the stacked propagator, for a matrix of 2n rows
+ * (a stacked matrix), a "shared" or Hermitian matrix, or a communicator of
+ * several ranks; then an open propagator stays as it was. */
+int cal_prop_begin_real(cal_ctx* ctx, int64_t n, const double* psi, int s, int max_blocks, const char* basis,
+                        const double* eigest, int neig);
+/* The real state's combine kernel (k_prop_combine_real) on host data, as
+ * cal_prop_combine_obs is for the stacked kernel: Q is n x m (ld n), a has m
+ * entries (m <= 512),
+ *   out[i] = sum_j Q[i,j] a_j     t = +0.0; j ascending: t = t + Q[i,j]*a_j
+ * *norm2 (may be NULL) = sum out^2 and, for k < nw <= 4, sums[k] = sum_i
+ * W_k[i] out[i]^2 (per row d = t*t; acc = acc + W_k[i]*d), both in the squared
+ * norm's fixed order.  W: n x nw column-major (NULL when nw = 0).
+ * Needs no matrix on the context.  The device copy of Q has the library's own
+ * padded leading dimension (16-byte accesses).  cal_prop_combine_real_ld takes
+ * Q with a host leading dimension ldq >= n and, when ldq > n, keeps it on the
+ * device: an odd ldq runs the kernel's 8-byte accesses. */
+int cal_prop_combine_real(cal_ctx* ctx, int64_t n, int m, const double* Q, const double* a, int nw, const double* W,
+                          double* out, double* norm2, double* sums);
+int cal_prop_combine_real_ld(cal_ctx* ctx, int64_t n, int m, const double* Q, int64_t ldq, const double* a, int nw,
+                             const double* W, double* out, double* norm2, double* sums);
 
 /* [T,Q,lsteps] = ca_lanczos_prop(A,r0,s,m,dt,tol,basis,eigest,adaptive)
  * (ca_lanczos_prop.m:3-135) with r0 = r_re + i r_im (r_im may be NULL) on the

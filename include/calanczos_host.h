@@ -54,6 +54,16 @@ int cal_qrstep(int m, double* H, int ldh, double* W, int ldw, double mu);
  * for a non-finite T. */
 int cal_expm_col1(int m, const double* T, int ldt, double dt, double* c_re, double* c_im);
 
+/* c = expm(-tau*(T - T(1,1)*I)) * e_1 for a general real m x m T (ldt >= m),
+ * 1 <= m <= 512: the coefficients of an imaginary-time step
+ * (cal_prop_set_imaginary_time), which renormalises and so uses only the
+ * direction of c; the shift by T(1,1) (the Rayleigh quotient of the step's
+ * start vector) keeps c away from over- and underflow.  T is taken as it
+ * comes, not symmetrised: scaling and squaring with a Taylor series in real
+ * arithmetic, no LAPACK.  Argument errors as cal_expm_col1; CAL_ERR_NUMERIC
+ * for a non-finite T or a result that overflows. */
+int cal_expm_real_col1(int m, const double* T, int ldt, double tau, double* c);
+
 /* Whether a CSR matrix (n rows, int64 row pointers, int32 sorted columns)
  * qualifies for the diagonal-split SpMV format (cal_set_spmv_format "split"):
  * 1 with the plane stride *P, the in-plane reach *H and *neg1 (every

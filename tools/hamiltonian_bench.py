@@ -6,6 +6,7 @@ the same matrix on CSR and against the plain Laplacian's plane march.
                                     [--only spmv,ca,lanczos,prop]
                                     [--library NAME] [--out profiles/dsplit/NAME.json]
                                     [--drive LIST] [--package-root DIR]
+                                    [--imaginary stacked,real]
 
 Matrix: grid_hamiltonian((N, N, N), V) with the harmonic potential V = 0.5 w^2
 |x - x0|^2 (w = 0.02: V of the size of the kinetic term), h = mass = 1, so the
@@ -52,6 +53,21 @@ child also reports the density kernel's own time (the "drive" timer class over
 route they replace -- state() back to the host, |psi|^2 and the new diagonal in
 NumPy, and a new Propagator on the rewritten matrix, every step (the frozen
 scheme; 2 steps per window).
+--imaginary LIST (stacked, real) adds prop legs in imaginary time, tau = --dt,
+each in a child of its own ("VARIANT+imstacked", "VARIANT+imreal"), and with
+--nonlinear frozen also under g |psi|^2 ("...+nlfrozen"): "stacked" is
+Propagator.set_imaginary_time on blkdiag(H, H), "real" is Propagator(...,
+real=True) on H itself.  Both start from the packet's real envelope |psi0| (a
+step's cost follows the state, so the two legs must relax the same one; the
+stacked leg's imaginary half then stays zero, which is the work the real path
+saves).  The summary's "imaginary_real_vs_stacked" has the ratio of the
+medians and, window class by window class, of the fastest and of the slowest
+windows.  The
+variant "auto" (format "auto") is there for the real leg: whatever the upload
+picks for H alone.  An imaginary child also times its combine kernel alone
+through the host-data entry (cal_prop_combine_real, n x 24, bytes (24 n + n) 8;
+cal_prop_combine, 2n x 24, bytes (48 n + 2n) 8; the library's "apply" timer
+brackets the kernel, three launches after a warm-up).
 --package-root DIR adds the undriven prop leg from another checkout's built
 package ("VARIANT@root", e.g. the parent commit's, to show it unchanged); for
 csr2 it adds every leg (the parent's stacked CSR, which shared is held against:
@@ -108,7 +124,7 @@ def child(a):
     N, W = a.N, a.windows
     A = build(cal, np, a.variant, N)
     n = A.shape[0]
-    fmt = {"split": "split", "csr": "csr", "lap": "auto", "shared": "shared", "csr2": "csr",
+    fmt = {"split": "split", "csr": "csr", "lap": "auto", "auto": "auto", "shared": "shared", "csr2": "csr",
            "herm": "shared", "herm_csr": "csr"}[a.variant]
     stacked = a.variant in STACKED
     ctx = cal.Context(spmv_format=fmt)
@@ -121,7 +137,7 @@ def child(a):
     else:
         ctx.set_matrix(A)
     out = dict(variant=a.variant, library=os.path.basename(_lib.LIB_PATH), package=os.path.relpath(os.path.dirname(cal.__file__), ROOT),
-               drive=a.drive, nonlinear=a.nonlinear, n=n, nnz=int(A.nnz),
+               drive=a.drive, nonlinear=a.nonlinear, imaginary=a.imaginary, n=n, nnz=int(A.nnz),
                spmv_format=ctx.spmv_format(), plane_info=ctx.spmv_plane_info(), split_info=ctx.spmv_split_info())
     if hasattr(ctx, "spmv_shared_info"):
         out["shared_info"] = ctx.spmv_shared_info()
@@ -175,7 +191,15 @@ def child(a):
         psi0 = np.exp(-r2 / (2 * (N / 8.0) ** 2)) * np.exp(1j * phase)
         del idx, coords, r2, phase
         ctx = cal.Context(spmv_format=fmt)
-        P = cal.Propagator(A, psi0, S, BLOCKS, basis="newton", ctx=ctx)
+        if a.imaginary != "0":  # both imaginary legs relax the same state: the packet's real envelope
+            psi0 = np.abs(psi0)
+        if a.imaginary == "real":  # on H itself
+            P = cal.Propagator(A, psi0, S, BLOCKS, basis="newton", ctx=ctx, real=True)
+            out["real_spmv_format"] = ctx.spmv_format()
+        else:
+            P = cal.Propagator(A, psi0, S, BLOCKS, basis="newton", ctx=ctx)
+            if a.imaginary == "stacked":
+                P.set_imaginary_time(True)
         out["stacked_split_info"] = ctx.spmv_split_info()
         out["stacked_plane_info"] = ctx.spmv_plane_info()
         nk = int(a.drive) if a.drive.isdigit() else 0
@@ -250,6 +274,9 @@ def child(a):
             us = 1e3 * tot / cnt
             out["drive_kernel"] = dict(us=us, launches_per_step=cnt / K, bytes=bytes_counted / cnt,
                                        TBps=bytes_counted / cnt / (us * 1e-6) / 1e12)
+        if a.imaginary != "0":
+            en = P.energetics()
+            out["energetics_last"] = {k: float(v[-1]) for k, v in en.items()}
         info = P.info()
         out["prop_ms_per_step"] = ms
         out["prop_lsteps"] = info["lsteps"]
@@ -259,11 +286,31 @@ def child(a):
         out["prop_info"] = {k: info[k] for k in ("steps", "lsteps_sum", "lsteps_max", "breakdowns", "rank_deficient")}
         out["prop_tsqr_fold_stats"] = ctx.tsqr_fold_stats()
         P.close()
+        if a.imaginary != "0":  # the combine kernel alone, on host data
+            m = S * BLOCKS
+            rows = n if a.imaginary == "real" else 2 * n
+            Q = np.empty((rows, m), order="F")
+            Q[:] = 1.0 / np.arange(1, m + 1)
+            co = np.cos(np.arange(m))
+            if a.imaginary == "real":
+                call, nbytes = (lambda: ctx.prop_combine_real(Q, co)), (n * m + n) * 8.0
+            else:
+                call, nbytes = (lambda: ctx.prop_combine(Q, co + 0.5j * co)), (2.0 * n * m + 2.0 * n) * 8.0
+            call()
+            ctx.timer_enable(True)
+            ctx.timer_reset()
+            for _ in range(3):
+                call()
+            cnt, tot = ctx.timer_read("apply")
+            ctx.timer_enable(False)
+            us = 1e3 * tot / cnt
+            out["combine_kernel"] = dict(us=us, launches=cnt, bytes=nbytes, TBps=nbytes / (us * 1e-6) / 1e12)
+            del Q
         ctx.close()
     print(json.dumps(out))
 
 
-def run_child(a, variant, drive="0", root=None, nonlinear="0"):
+def run_child(a, variant, drive="0", root=None, nonlinear="0", imaginary="0"):
     env = dict(os.environ)
     env.pop("CAL_LIBRARY", None)
     env.pop("CAL_SPMV_FORMAT", None)
@@ -271,15 +318,16 @@ def run_child(a, variant, drive="0", root=None, nonlinear="0"):
         env["CAL_LIBRARY"] = a.library
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--variant", variant, "--N", str(a.N),
            "--windows", str(a.windows), "--only",
-           a.only if drive == "0" and nonlinear == "0" and (not root or variant in STACKED) else "prop",
+           a.only if drive == "0" and nonlinear == "0" and imaginary == "0" and (not root or variant in STACKED)
+           else "prop",
            "--dt", str(a.dt),
-           "--drive", drive, "--nonlinear", nonlinear]
+           "--drive", drive, "--nonlinear", nonlinear, "--imaginary", imaginary]
     if root:
         cmd += ["--package-root", root]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
     if p.returncode != 0:
-        raise RuntimeError("child %s drive %s nonlinear %s failed (%d): %s"
-                           % (variant, drive, nonlinear, p.returncode, p.stderr[-2000:]))
+        raise RuntimeError("child %s drive %s nonlinear %s imaginary %s failed (%d): %s"
+                           % (variant, drive, nonlinear, imaginary, p.returncode, p.stderr[-2000:]))
     return json.loads(p.stdout.strip().splitlines()[-1])
 
 
@@ -294,6 +342,7 @@ def main():
     ap.add_argument("--library", default=None)
     ap.add_argument("--drive", default="0", help="prop leg: comma list of 0, 1..4 (operators) or reupload")
     ap.add_argument("--nonlinear", default="0", help="prop leg: comma list of frozen, midpoint, copyback")
+    ap.add_argument("--imaginary", default="0", help="prop leg in imaginary time: comma list of stacked, real")
     ap.add_argument("--package-root", default=None, help="also the undriven prop leg from this checkout's package")
     ap.add_argument("--child-timeout", type=int, default=500)
     ap.add_argument("--variant", default=None, help=argparse.SUPPRESS)
@@ -314,17 +363,31 @@ def main():
     for x in nls:
         if x not in ("frozen", "midpoint", "copyback"):
             ap.error("--nonlinear takes frozen, midpoint or copyback")
-    legs = [(v, v, "0", None, "0") for v in variants] if "0" in drives else []
-    legs += [("%s+drive%s" % (v, d), v, d, None, "0") for v in variants if v != "lap" for d in drives if d != "0"]
-    legs += [("%s+nl%s" % (v, x), v, "0", None, x) for v in variants if v != "lap" for x in nls]
+    ims = [x for x in a.imaginary.split(",") if x != "0"]
+    for x in ims:
+        if x not in ("stacked", "real"):
+            ap.error("--imaginary takes stacked or real")
+    # the real-time legs; "auto" exists for the real imaginary leg alone
+    legs = [(v, v, "0", None, "0", "0") for v in variants if v != "auto"] if "0" in drives else []
+    legs += [("%s+drive%s" % (v, d), v, d, None, "0", "0") for v in variants if v not in ("lap", "auto")
+             for d in drives if d != "0"]
+    legs += [("%s+nl%s" % (v, x), v, "0", None, x, "0") for v in variants if v not in ("lap", "auto") for x in nls]
+    for v in variants:
+        for im in ims:
+            if v == "lap" or (im == "real" and v in STACKED) or (im == "stacked" and v == "auto"):
+                continue
+            legs.append(("%s+im%s" % (v, im), v, "0", None, "0", im))
+            if "frozen" in nls and v != "auto":  # the density kernel rewrites a stored diagonal ("csr" / "split")
+                legs.append(("%s+im%s+nlfrozen" % (v, im), v, "0", None, "frozen", im))
     if a.package_root:
-        legs += [("%s@root" % v, v, "0", a.package_root, "0") for v in variants if v != "shared" and v not in HERM]
+        legs += [("%s@root" % v, v, "0", a.package_root, "0", "0") for v in variants
+                 if v not in ("shared", "auto") and v not in HERM]
     variants = [l[0] for l in legs]
     res = dict(N=a.N, n=a.N ** 3, rounds=a.rounds, windows=a.windows, only=a.only, library=a.library or "production",
                s=S, blocks=BLOCKS, runs={v: [] for v in variants})
     for i in range(a.rounds):  # alternating, each in a fresh process
-        for name, v, d, root, nl in legs:
-            res["runs"][name].append(run_child(a, v, d, root, nl))
+        for name, v, d, root, nl, im in legs:
+            res["runs"][name].append(run_child(a, v, d, root, nl, im))
             print("round %d: %s done" % (i + 1, name), file=sys.stderr, flush=True)
 
     keys = dict(spmv="spmv_us", ca="ca_ms_per_outer", lanczos="lanczos_ms_per_vector", prop="prop_ms_per_step")
@@ -342,7 +405,25 @@ def main():
             summ[v]["drive_kernel"] = dict(us=statistics.median(x["us"] for x in dk), us_all=[x["us"] for x in dk],
                                            bytes=dk[0]["bytes"], launches_per_step=dk[0]["launches_per_step"],
                                            TBps=dk[0]["bytes"] / (statistics.median(x["us"] for x in dk) * 1e-6) / 1e12)
+        ck = [r["combine_kernel"] for r in res["runs"][v] if "combine_kernel" in r]
+        if ck:
+            us = statistics.median(x["us"] for x in ck)
+            summ[v]["combine_kernel"] = dict(us=us, us_all=[x["us"] for x in ck], bytes=ck[0]["bytes"],
+                                             TBps=ck[0]["bytes"] / (us * 1e-6) / 1e12)
     res["summary"] = summ
+    # the real path against the stacked one, leg by leg: the byte ratio says 2
+    res["imaginary_real_vs_stacked"] = {}
+    for v in variants:
+        if "+imreal" in v and "prop" in summ[v]:
+            other = v.replace("+imreal", "+imstacked")
+            if other.startswith("auto+"):
+                other = "split+" + other.split("+", 1)[1]
+            if other in summ and "prop" in summ[other]:
+                res["imaginary_real_vs_stacked"][v] = dict(
+                    against=other, ratio=summ[other]["prop"]["median"] / summ[v]["prop"]["median"],
+                    ratio_fastest_windows=summ[other]["prop"]["min"] / summ[v]["prop"]["min"],
+                    ratio_slowest_windows=summ[other]["prop"]["max"] / summ[v]["prop"]["max"],
+                    slowest_real_beats_fastest_stacked=bool(summ[v]["prop"]["max"] < summ[other]["prop"]["min"]))
     n = a.N ** 3
     for v in variants:
         if "spmv" in summ[v]:
