@@ -1168,18 +1168,25 @@ class Propagator:
               "prop_set_nonlinear")
         return self
 
+    def _history(self, getter, name, first, count, ncols=None):
+        """Rows [first, first + count) (count None: all from first) of one of
+        the per-step histories: a first call for the row count (and, with
+        ``ncols`` None, the column count the getter reports), a second for
+        the rows."""
+        nr, nc = ctypes.c_int64(), ctypes.c_int()
+        tail = (ctypes.byref(nr),) if ncols is not None else (ctypes.byref(nr), ctypes.byref(nc))
+        check(self.ctx.h, getter(self.ctx.h, 0, 0, None, *tail), name)
+        count = nr.value - first if count is None else count
+        rows = np.zeros((max(count, 0), nc.value if ncols is None else ncols))
+        check(self.ctx.h, getter(self.ctx.h, int(first), int(count), ptr(rows), *tail), name)
+        return rows
+
     def nonlinear(self, first=0, count=None):
         """One row ``[t_n, sum_i |psi_n,i|^4]`` per completed step since
         ``set_nonlinear`` (rows [first, first + count); default all), psi_n
         the state the step started from: ``g/2`` times the second column is
         the interaction energy.  Shape (rows, 2)."""
-        nr = ctypes.c_int64()
-        check(self.ctx.h, lib.cal_prop_get_nonlinear(self.ctx.h, 0, 0, None, ctypes.byref(nr)), "prop_get_nonlinear")
-        count = nr.value - first if count is None else count
-        rows = np.zeros((max(count, 0), 2))
-        check(self.ctx.h, lib.cal_prop_get_nonlinear(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr)),
-              "prop_get_nonlinear")
-        return rows
+        return self._history(lib.cal_prop_get_nonlinear, "prop_get_nonlinear", first, count, 2)
 
     def set_imaginary_time(self, on=True):
         """From now on ``step`` takes ``dt`` as an imaginary-time step tau:
@@ -1201,12 +1208,7 @@ class Propagator:
         energy: conserved in real time) and ``residual``
         (``||H[psi_n] psi_n - mu psi_n|| / sqrt(N_n)``).  They are read off
         the first column of the step's Krylov matrix: no kernel, no sweep."""
-        nr = ctypes.c_int64()
-        check(self.ctx.h, lib.cal_prop_get_energetics(self.ctx.h, 0, 0, None, ctypes.byref(nr)), "prop_get_energetics")
-        count = nr.value - first if count is None else count
-        rows = np.zeros((max(count, 0), 5))
-        check(self.ctx.h, lib.cal_prop_get_energetics(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr)),
-              "prop_get_energetics")
+        rows = self._history(lib.cal_prop_get_energetics, "prop_get_energetics", first, count, 5)
         return dict(t=rows[:, 0].copy(), norm2=rows[:, 1].copy(), mu=rows[:, 2].copy(), energy=rows[:, 3].copy(),
                     residual=rows[:, 4].copy())
 
@@ -1251,13 +1253,7 @@ class Propagator:
         step (rows [first, first + count); default all): dict of ``t``,
         ``norm2``, ``energy`` (NaN when off), ``W`` (steps x nw) and
         ``overlap`` (steps x nphi, complex)."""
-        nr, nc = ctypes.c_int64(), ctypes.c_int()
-        check(self.ctx.h, lib.cal_prop_get_observables(self.ctx.h, 0, 0, None, ctypes.byref(nr), ctypes.byref(nc)),
-              "prop_get_observables")
-        count = nr.value - first if count is None else count
-        rows = np.zeros((max(count, 0), nc.value))
-        check(self.ctx.h, lib.cal_prop_get_observables(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr),
-                                                       ctypes.byref(nc)), "prop_get_observables")
+        rows = self._history(lib.cal_prop_get_observables, "prop_get_observables", first, count)
         nw = self._nw  # the W columns come first, then the (Re, Im) pairs
         ov = rows[:, 3 + nw:]
         return dict(t=rows[:, 0].copy(), norm2=rows[:, 1].copy(), energy=rows[:, 2].copy(),
@@ -1288,12 +1284,7 @@ class Propagator:
         """The squared norm the mask removed, one entry per completed step
         since ``set_absorber`` (rows [first, first + count); default all):
         dict of ``t`` and ``absorbed``."""
-        nr = ctypes.c_int64()
-        check(self.ctx.h, lib.cal_prop_get_absorbed(self.ctx.h, 0, 0, None, ctypes.byref(nr)), "prop_get_absorbed")
-        count = nr.value - first if count is None else count
-        rows = np.zeros((max(count, 0), 2))
-        check(self.ctx.h, lib.cal_prop_get_absorbed(self.ctx.h, int(first), int(count), ptr(rows), ctypes.byref(nr)),
-              "prop_get_absorbed")
+        rows = self._history(lib.cal_prop_get_absorbed, "prop_get_absorbed", first, count, 2)
         return dict(t=rows[:, 0].copy(), absorbed=rows[:, 1].copy())
 
     def close(self):

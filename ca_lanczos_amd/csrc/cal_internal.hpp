@@ -584,7 +584,7 @@ struct PropCombine {
     PropObs obs;                   // zero counts: none
     const double* mask = nullptr;  // null: none
     int64_t ldm = 0;
-    // a real state (k_prop_combine_real): out[i] = sum_j Q[i,j] a_j for i < n,
+    // a real state (k_prop_combine's REAL flag): out[i] = sum_j Q[i,j] a_j for i < n,
     // ld >= n, b unused, nw observables allowed (the chain d = t*t;
     // acc = acc + W_k[i]*d), no reference states and no mask
     bool real = false;
@@ -601,11 +601,22 @@ hipError_t launch_prop_combine(const PropCombine& p, hipStream_t st);
 // launch_reduce(partial, blocks, 2, ...) sums both).
 int diag_find_blocks(int64_t n);
 hipError_t launch_diag_find(const int* rowptr, const int* col, int64_t n, int* dpos, double* partial, hipStream_t st);
-// k_diag_drive: for i < n
+// k_diag_density, the one kernel that rewrites the diagonal: for i < n
 //   d = V0[i];  for k = 0 .. nk-1 (ascending):  p = f[k] * W[i + k ldw];  d = d + p
 // (product and sum round separately), then val[dpos[i + h n]] = d and, with
 // ds_diag non-null, ds_diag[i + h n] = d for h < halves (1 or 2).  nk <=
 // kDriveMaxOps; every dpos entry must be a valid position (dpos_state == 1).
+// A null: that is all (the drive alone; B must be null, partial may be).
+// A non-null adds a nonlinear term of one state A = ua + i va (B null) or of
+// two (B = ub + i vb), each a stacked device vector (Re in [0, n), Im in
+// [n, 2n)); every product and sum rounded separately,
+//   ra = ua*ua;  ra = ra + va*va;  rb = ub*ub;  rb = rb + vb*vb   (rb: B only)
+//   the chain into d above
+//   p = ga*ra;  d = d + p;  p = gb*rb;  d = d + p                 (gb: B only)
+// then the stores of d, and q = ra*ra summed over the block's rows (wave tree,
+// the four waves in order) into partial[block], block <
+// diag_density_blocks(n): launch_reduce(partial, blocks, 1, ...) gives
+// sum_i |A_i|^4.  One launch writes the drive and the density together.
 constexpr int kDriveMaxOps = 4;
 struct DiagDrive {
     const double* V0 = nullptr;
@@ -616,31 +627,16 @@ struct DiagDrive {
     const int* dpos = nullptr;
     double* val = nullptr;
     double* ds_diag = nullptr;
-};
-hipError_t launch_diag_drive(const DiagDrive& a, hipStream_t st);
-// k_diag_density: k_diag_drive's diagonal plus a nonlinear term of one state
-// A = ua + i va (B null) or of two (B = ub + i vb), each a stacked device
-// vector (Re in [0, n), Im in [n, 2n)); for i < n, every product and sum
-// rounded separately,
-//   ra = ua*ua;  ra = ra + va*va;  rb = ub*ub;  rb = rb + vb*vb   (rb: B only)
-//   d = V0[i];  for k ascending:  p = f[k] * W[i + k ldw];  d = d + p
-//   p = ga*ra;  d = d + p;  p = gb*rb;  d = d + p                 (gb: B only)
-// then k_diag_drive's stores of d, and q = ra*ra summed over the block's rows
-// (wave tree, the four waves in order) into partial[block], block <
-// diag_density_blocks(n): launch_reduce(partial, blocks, 1, ...) gives
-// sum_i |A_i|^4.  One launch writes the drive and the density together.
-struct DiagDensity {
-    DiagDrive d;
-    const double* A = nullptr;
+    const double* A = nullptr;  // null: no state
     const double* B = nullptr;  // null: one state
     double ga = 0.0, gb = 0.0;
     double* partial = nullptr;
     // real states of n rows (cal_prop_begin_real): ra = ua*ua, rb = ub*ub, no
-    // lower half is read; d.halves must be 1
+    // lower half is read; halves must be 1
     bool real = false;
 };
-int diag_density_blocks(int64_t n);
-hipError_t launch_diag_density(const DiagDensity& a, hipStream_t st);
+int diag_density_blocks(int64_t n);  // the launch's grid, with or without a state
+hipError_t launch_diag_density(const DiagDrive& a, hipStream_t st);
 
 
 }  // namespace cal
@@ -648,7 +644,7 @@ hipError_t launch_diag_density(const DiagDensity& a, hipStream_t st);
 // Per-launch kernel timer (HIP events on the launching stream).
 struct CalTimerRec {
     int kind;  // 0 spmv, 1 gram, 2 apply, 3 other, 4 allreduce (RCCL), 5 halo exchange (RCCL), 6 normest,
-               // 7 drive (k_diag_drive: the diagonal rewritten by cal_set_diagonal / a driven time step)
+               // 7 drive (k_diag_density: the diagonal rewritten by cal_set_diagonal / a driven time step)
     hipEvent_t a, b;
     double bytes;  // the launch's algorithmic HBM bytes, 0 if not stated
 };
@@ -969,17 +965,18 @@ hipError_t spmv_on_stream(const cal_ctx* c, const double* x, double* y, int mode
 // diag_positions: finds the positions once per uploaded matrix (one host wait
 // for the two counts) and answers from the cached verdict afterwards.
 int diag_positions(cal_ctx* c);
-// H's diagonal <- V0 + sum_k f[k] W(:, k) (launch_diag_drive; V0 / W on the
-// device, f on the host; n = n_local / halves) into val and, on the split
-// format, ds_diag; enqueued on the stream, no host wait once the positions exist
+// H's diagonal <- V0 + sum_k f[k] W(:, k) (launch_diag_density without a state;
+// V0 / W on the device, f on the host; n = n_local / halves) into val and, on
+// the split format, ds_diag; enqueued on the stream, no host wait once the
+// positions exist
 int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
                     const double* f);
-// diag_update_dev with the nonlinear term of launch_diag_density in the same
-// launch: H's diagonal <- V0 + sum_k f[k] W(:, k) + ga |A|^2 (+ gb |B|^2, B
-// non-null), A / B stacked device states of 2n doubles; the blocks' shares of
-// sum_i |A_i|^4 go to partial (diag_density_blocks(n) doubles, the caller's).
-// Same positions, same rule for a shared matrix, timed as the drive is.
-// halves = 1: A_dev / B_dev are real states of n rows (DiagDensity::real).
+// diag_update_dev with the nonlinear term in the same launch (both are calls
+// of one routine): H's diagonal <- V0 + sum_k f[k] W(:, k) + ga |A|^2 (+ gb
+// |B|^2, B non-null), A / B stacked device states of 2n doubles; the blocks'
+// shares of sum_i |A_i|^4 go to partial (diag_density_blocks(n) doubles, the
+// caller's).  halves = 1: A_dev / B_dev are real states of n rows
+// (DiagDrive::real).
 int diag_density_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
                      const double* f, const double* A_dev, double ga, const double* B_dev, double gb, double* partial);
 // dst[i] = val[dpos[i]], i < cnt <= n_local (device dst; enqueued)

@@ -16,11 +16,11 @@
 // serve every later one (runLanczos.m:93-96 passes eigest the same way).
 // A time-dependent potential H(t) = H0 + sum_k f_k(t) diag(W_k)
 // (cal_prop_set_drive / cal_prop_step_driven) rewrites the matrix's stored
-// diagonal in place before each step (prop.hip k_diag_drive through
-// runtime.cpp diag_update_dev): the step itself is unchanged.
+// diagonal in place before each step (prop.hip k_diag_density without a state,
+// through runtime.cpp diag_update_dev): the step itself is unchanged.
 // A nonlinear term g |psi|^2 (cal_prop_set_nonlinear; Gross-Pitaevskii) adds
-// the state's density to that diagonal on the device (prop.hip k_diag_density
-// through runtime.cpp diag_density_dev, the drive in the same launch): once
+// the state's density to that diagonal on the device (the same kernel with one
+// state or two, through diag_density_dev, the drive in the same launch): once
 // per step with the density of psi_n ("frozen", first order), or twice
 // ("midpoint": a frozen step predicts psi* into a second buffer, then the step
 // proper runs from psi_n under the mean of both densities; second order, two
@@ -34,7 +34,12 @@
 // H[psi]) psi / ||.||, whose fixed point is the ground state.  A real H has a
 // real ground state: cal_prop_begin_real runs the same host path on H itself
 // (PropState::halves = 1), the state one real vector of n rows, the combine
-// k_prop_combine_real and the density k_diag_density's REAL instantiation.
+// and the density the REAL instantiations of k_prop_combine and k_diag_density.
+// The host path is written once: combine_launch sizes, times, launches and
+// reduces a filled PropCombine for combine_dev (the step's sweep and, as an
+// option, the midpoint predictor's) and for combine_host (the five
+// cal_prop_combine* exports, stacked and real); krylov_scaled is a build with
+// its refusal and scaling; history_rows serves the four cal_prop_get_* getters.
 // Every step also records [t_n, N_n, mu_n, E_n, res_n] from the first column
 // of its first build's T (cal_prop_get_energetics): no kernel, no sweep.
 // The one deliberate difference from ca_lanczos_prop.m: :78 projects with
@@ -274,13 +279,37 @@ void prop_free(cal_ctx* c) {
     c->prop = nullptr;
 }
 
+// One combine sweep from a filled PropCombine (all but its partial): sizes
+// d_partial (the sweep's quantities x blocks, then `extra` doubles of the
+// caller's) and d_red (nred doubles; 0: nothing is reduced), launches under the
+// "apply" timer with the sweep's bytes and reduces the quantities into d_red
+int combine_launch(cal_ctx* c, PropCombine& k, size_t extra, int nred) {
+    const int nb = prop_combine_blocks(k.n);
+    const int nk = prop_combine_quantities(k);
+    CAL_TRY(ensure_partial(c, (size_t)nk * nb + extra));
+    if (nred > 0) CAL_TRY(ensure_red(c, (size_t)nred));
+    k.partial = c->d_partial;
+    const double rows = (double)(k.real ? 1 : 2) * k.n;  // of Q's columns and of out
+    const int t = timer_begin(c, 2, (rows * k.m + rows + (double)k.n * (nk - 1)) * 8.0);
+    const hipError_t e = launch_prop_combine(k, c->stream);
+    timer_end(c, t);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
+    if (nred > 0) CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, nk, c->d_red, c->stream));
+    return 0;
+}
+
 // psi <- Q(:, 0:m) (a + i b) and nrm2 <- psi'psi (a, b: Re / Im of nrm c, on the host);
-// a real state (halves == 1): psi <- Q(:, 0:m) a through k_prop_combine_real
-int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, const double* a, const double* b) {
-    std::memcpy(P.h_coef, a, m * sizeof(double));
-    std::memcpy(P.h_coef + kPropMaxCols, b, m * sizeof(double));
-    CAL_HIP_OTHER(c, hipMemcpyAsync(P.d_coef, P.h_coef, 2 * kPropMaxCols * sizeof(double), hipMemcpyHostToDevice,
-                                    c->stream));
+// a real state (halves == 1): psi <- Q(:, 0:m) a through k_prop_combine's REAL flag.
+// predict: the midpoint predictor's sweep, d_psi2 <- Q(:, 0:m) (a + i b) -- the
+// plain sweep (no observables, no mask), nothing reduced and no host wait: the
+// corrector's density launch follows it on the stream.  Its coefficients are
+// staged in h_coef2: h_coef is the step proper's.
+int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, const double* a, const double* b,
+                bool predict = false) {
+    double* hc = predict ? P.h_coef2 : P.h_coef;
+    std::memcpy(hc, a, m * sizeof(double));
+    std::memcpy(hc + kPropMaxCols, b, m * sizeof(double));
+    CAL_HIP_OTHER(c, hipMemcpyAsync(P.d_coef, hc, 2 * kPropMaxCols * sizeof(double), hipMemcpyHostToDevice, c->stream));
     PropCombine k;
     k.Q = Q;
     k.ld = ld;
@@ -288,24 +317,20 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     k.m = m;
     k.a = P.d_coef;
     k.b = P.d_coef + kPropMaxCols;
+    k.real = P.halves == 1;
+    if (predict) {  // the provisional state's norm is not used
+        k.out = P.d_psi2 + c->A.lpad;
+        return combine_launch(c, k, 0, 0);
+    }
     k.out = P.psi(c);
     k.obs = make_obs(P.d_obs, P.ldo, P.nw, P.nphi);
     k.mask = P.d_mask;
     k.ldm = P.ldm;
-    k.real = P.halves == 1;
-    const int nb = prop_combine_blocks(P.n);
-    const int nk = prop_combine_quantities(k);
     const int nd = dot_blocks(P.rows());
-    const size_t pe = (size_t)nk * nb;  // the energy's partials follow the combine's
-    CAL_TRY(ensure_partial(c, pe + (P.energy ? (size_t)std::max(P.eparts, nd) : 0)));
+    // the energy's partials follow the combine's
+    const size_t pe = (size_t)prop_combine_quantities(k) * prop_combine_blocks(P.n);
     const int nred = P.red_count() + (P.nl_on() ? 1 : 0);  // the nonlinear term's sum |psi_n|^4 comes last
-    CAL_TRY(ensure_red(c, (size_t)nred));
-    k.partial = c->d_partial;
-    const int t = timer_begin(c, 2, ((double)P.rows() * m + (double)P.rows() + (double)P.n * (nk - 1)) * 8.0);
-    const hipError_t e = launch_prop_combine(k, c->stream);
-    timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, nk, c->d_red, c->stream));
+    CAL_TRY(combine_launch(c, k, P.energy ? (size_t)std::max(P.eparts, nd) : 0, nred));
     if (P.nl_on()) CAL_HIP_OTHER(c, launch_reduce(P.d_nlpart, P.nl_nb, 1, c->d_red + P.red_count(), c->stream));
     if (P.energy) {
         // <psi'|H|psi'> = y'x over the stacked rows, y = blkdiag(H, H) x: the
@@ -326,35 +351,6 @@ int combine_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, co
     CAL_HIP_OTHER(c, hipMemcpyAsync(h, c->d_red, (size_t)nred * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     CAL_HIP(c, hipStreamSynchronize(c->stream));
     P.nrm2 = h[0];
-    return 0;
-}
-
-// the predictor's combine: d_psi2 <- Q(:, 0:m) (a + i b), the plain sweep (no
-// observables, no mask), nothing reduced and no host wait -- the corrector's
-// density launch follows it on the stream.  The coefficients are staged in
-// h_coef2: h_coef is the step proper's.
-int combine_predict_dev(cal_ctx* c, PropState& P, const double* Q, int64_t ld, int m, const double* a,
-                        const double* b) {
-    std::memcpy(P.h_coef2, a, m * sizeof(double));
-    std::memcpy(P.h_coef2 + kPropMaxCols, b, m * sizeof(double));
-    CAL_HIP_OTHER(c, hipMemcpyAsync(P.d_coef, P.h_coef2, 2 * kPropMaxCols * sizeof(double), hipMemcpyHostToDevice,
-                                    c->stream));
-    PropCombine k;
-    k.Q = Q;
-    k.ld = ld;
-    k.n = P.n;
-    k.m = m;
-    k.a = P.d_coef;
-    k.b = P.d_coef + kPropMaxCols;
-    k.out = P.d_psi2 + c->A.lpad;
-    k.real = P.halves == 1;
-    const int nb = prop_combine_blocks(P.n);
-    CAL_TRY(ensure_partial(c, (size_t)nb));
-    k.partial = c->d_partial;  // the provisional state's norm is not used
-    const int t = timer_begin(c, 2, ((double)P.rows() * m + (double)P.rows()) * 8.0);
-    const hipError_t e = launch_prop_combine(k, c->stream);
-    timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
     return 0;
 }
 
@@ -461,6 +457,24 @@ int krylov(cal_ctx* c, PropState& P, double dt, double tol, int adaptive, int* k
     return 0;
 }
 
+// krylov with what every caller does next: no usable block is refused with
+// CAL_WARN_BREAKDOWN under the caller's message (the state is unchanged);
+// otherwise *ks = s kuse and cre / cim are scaled to the combine's
+// coefficients, nrm c (imaginary time: sqrt(N0) c / ||c||)
+int krylov_scaled(cal_ctx* c, PropState& P, double dt, double tol, int adaptive, const std::string& broke, int* ks,
+                  std::vector<double>& cre, std::vector<double>& cim, double* resid, double* en) {
+    int kuse = 0;
+    double scale = 0.0;
+    CAL_TRY(krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, resid, &scale, en));
+    if (kuse == 0) return set_error(c, CAL_WARN_BREAKDOWN, broke);
+    *ks = kuse * P.s;
+    for (int j = 0; j < *ks; ++j) {
+        cre[j] = scale * cre[j];
+        cim[j] = scale * cim[j];
+    }
+    return 0;
+}
+
 int check_prop_args(cal_ctx* c, int64_t n, int halves, int s, int max_blocks, const char* basis, bool* newton) {
     if (!c) return CAL_ERR_ARG;
     hipSetDevice(c->device);
@@ -516,48 +530,50 @@ bool mask_ok(const double* mask, int64_t n) {
 }
 
 // The combine sweep on host data, behind the cal_prop_combine* exports (which
-// check the arguments): mask null for none, nw = nphi = 0 for no observables.
-// d_scratch holds [Q (ld x m) | out (ld) | W and phi (ldo x nq) | the mask
-// (ldo, when given) | the coefficients (2 m)], ld and ldo multiples of 64, so
-// every origin is 16-byte aligned.
-int combine_host(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
-                 const double* mask, int nw, const double* W, int nphi, const double* phi_re, const double* phi_im,
-                 double* out_re, double* out_im, double* norm2, double* absorbed, double* sums) {
+// check the arguments): halves = 2 the stacked sweep (Q of 2n rows, c_re +
+// i c_im), halves = 1 the real state's (Q of n rows, c_re alone; no mask, no
+// reference states); mask null for none, nw = nphi = 0 for no observables.
+// Q has the host leading dimension ldq >= halves n.  ldq == halves n: the
+// device copy takes the library's own padded leading dimension (a multiple of
+// 64: the 16-byte path, and the stacked lower half misaligned exactly when n is
+// odd).  ldq > halves n: the copy keeps ldq, so an odd ldq runs the 8-byte path.
+// d_scratch holds [out (ldv) | W and phi (ldo x nq) | the mask (ldo, when
+// given) | the coefficients (halves m, rounded up to even) | Q (ld x m)], ldv
+// and ldo multiples of 64: every origin is 16-byte aligned.
+int combine_host(cal_ctx* c, int64_t n, int halves, int m, const double* Q, int64_t ldq, const double* c_re,
+                 const double* c_im, const double* mask, int nw, const double* W, int nphi, const double* phi_re,
+                 const double* phi_im, double* out_re, double* out_im, double* norm2, double* absorbed, double* sums) {
     const int nq = nw + 2 * nphi, na = mask ? 1 : 0;
-    const int64_t ld = pad64(2 * n), ldo = pad64(n);
-    CAL_TRY(ensure_scratch(c, (size_t)ld * (m + 1) + (size_t)ldo * (nq + na) + 2 * (size_t)m));
-    double* dobs = c->d_scratch + (size_t)ld * (m + 1);
+    const int64_t rows = halves * n, ldv = pad64(rows), ldo = pad64(n), ld = ldq == rows ? ldv : ldq;
+    const size_t mc = (size_t)halves * m + (halves * m & 1);
+    CAL_TRY(ensure_scratch(c, (size_t)ldv + (size_t)ldo * (nq + na) + mc + (size_t)ld * m));
+    double* dout = c->d_scratch;
+    double* dobs = dout + ldv;
     double* dmask = dobs + (size_t)ldo * nq;
     double* dco = dmask + (size_t)ldo * na;
+    double* dq = dco + mc;
     PropCombine k;
-    k.Q = c->d_scratch;
+    k.Q = dq;
     k.ld = ld;
     k.n = n;
     k.m = m;
     k.a = dco;
     k.b = dco + m;
-    k.out = c->d_scratch + (size_t)ld * m;
+    k.out = dout;
     k.obs = make_obs(dobs, ldo, nw, nphi);
     k.mask = mask ? dmask : nullptr;
     k.ldm = ldo;
-    const int nb = prop_combine_blocks(n);
-    const int nk = prop_combine_quantities(k);
-    CAL_TRY(ensure_partial(c, (size_t)nk * nb));
-    CAL_TRY(ensure_red(c, (size_t)nk));
-    k.partial = c->d_partial;
-    CAL_HIP(c, hipMemcpy2DAsync(c->d_scratch, ld * sizeof(double), Q, 2 * n * sizeof(double), 2 * n * sizeof(double),
-                                m, hipMemcpyHostToDevice, c->stream));
+    k.real = halves == 1;
+    CAL_HIP(c, hipMemcpy2DAsync(dq, ld * sizeof(double), Q, ldq * sizeof(double), rows * sizeof(double), m,
+                                hipMemcpyHostToDevice, c->stream));
     CAL_HIP(c, hipMemcpyAsync(dco, c_re, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (halves == 2) CAL_HIP(c, hipMemcpyAsync(dco + m, c_im, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (mask) CAL_HIP(c, hipMemcpyAsync(dmask, mask, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CAL_TRY(upload_obs(c, dobs, ldo, n, nw, W, nphi, phi_re, phi_im));
-    const int t = timer_begin(c, 2, ((double)2 * n * m + (double)2 * n + (double)n * (nk - 1)) * 8.0);
-    const hipError_t e = launch_prop_combine(k, c->stream);
-    timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, nk, c->d_red, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out_re, k.out, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out_im, k.out + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const int nk = prop_combine_quantities(k);
+    CAL_TRY(combine_launch(c, k, 0, nk));
+    CAL_HIP(c, hipMemcpyAsync(out_re, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (halves == 2) CAL_HIP(c, hipMemcpyAsync(out_im, dout + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     double red[2 + 3 * kPropMaxObs] = {0.0};
     CAL_HIP(c, hipMemcpyAsync(red, c->d_red, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     CAL_HIP(c, hipStreamSynchronize(c->stream));
@@ -567,50 +583,16 @@ int combine_host(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_
     return 0;
 }
 
-// The real state's sweep on host data, behind cal_prop_combine_real / _ld.  Q
-// has the host leading dimension ldq >= n.  ldq == n: the device copy takes
-// the library's own padded leading dimension (a multiple of 64: the 16-byte
-// path).  ldq > n: the copy keeps ldq, so an odd ldq runs the 8-byte path.
-// d_scratch holds [out (ldo) | W (ldo x nw) | a (m rounded up to even) | Q
-// (ld x m)], ldo a multiple of 64: every origin is 16-byte aligned.
-int combine_real_host(cal_ctx* c, int64_t n, int m, const double* Q, int64_t ldq, const double* a, int nw,
-                      const double* W, double* out, double* norm2, double* sums) {
-    const int64_t ldo = pad64(n), ld = ldq == n ? ldo : ldq;
-    const size_t ma = (size_t)m + (m & 1);
-    CAL_TRY(ensure_scratch(c, (size_t)ldo * (1 + nw) + ma + (size_t)ld * m));
-    double* dout = c->d_scratch;
-    double* dobs = dout + ldo;
-    double* dco = dobs + (size_t)ldo * nw;
-    double* dq = dco + ma;
-    PropCombine k;
-    k.Q = dq;
-    k.ld = ld;
-    k.n = n;
-    k.m = m;
-    k.a = dco;
-    k.out = dout;
-    k.obs = make_obs(dobs, ldo, nw, 0);
-    k.real = true;
-    const int nb = prop_combine_blocks(n);
-    const int nk = prop_combine_quantities(k);
-    CAL_TRY(ensure_partial(c, (size_t)nk * nb));
-    CAL_TRY(ensure_red(c, (size_t)nk));
-    k.partial = c->d_partial;
-    CAL_HIP(c, hipMemcpy2DAsync(dq, ld * sizeof(double), Q, ldq * sizeof(double), n * sizeof(double), m,
-                                hipMemcpyHostToDevice, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(dco, a, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CAL_TRY(upload_cols(c, dobs, ldo, W, n, nw));
-    const int t = timer_begin(c, 2, ((double)n * m + (double)n + (double)n * nw) * 8.0);
-    const hipError_t e = launch_prop_combine(k, c->stream);
-    timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_prop_combine");
-    CAL_HIP_OTHER(c, launch_reduce(c->d_partial, nb, nk, c->d_red, c->stream));
-    CAL_HIP(c, hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    double red[1 + kPropMaxObs] = {0.0};
-    CAL_HIP(c, hipMemcpyAsync(red, c->d_red, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CAL_HIP(c, hipStreamSynchronize(c->stream));
-    if (norm2) *norm2 = red[0];
-    for (int q = 0; q < nw; ++q) sums[q] = red[1 + q];
+// rows [first, first + count) of a per-step history of nc columns, behind the
+// four cal_prop_get_* exports; out null: the row count alone
+int history_rows(cal_ctx* c, const std::string& who, const std::vector<double>& hist, int nc, int64_t first,
+                 int64_t count, double* out, int64_t* nrows) {
+    const int64_t nr = (int64_t)(hist.size() / nc);
+    if (nrows) *nrows = nr;
+    if (!out) return 0;
+    if (first < 0 || count < 0 || first + count > nr)
+        return set_error(c, CAL_ERR_ARG, who + ": rows [first, first + count) out of range");
+    std::memcpy(out, hist.data() + (size_t)first * nc, (size_t)count * nc * sizeof(double));
     return 0;
 }
 
@@ -737,8 +719,8 @@ int cal_prop_combine(cal_ctx* c, int64_t n, int m, const double* Q, const double
     hipSetDevice(c->device);
     if (!combine_args_ok(n, m, Q, c_re, c_im, out_re, out_im))
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine: need n >= 1, 1 <= m <= 512 and non-null arrays");
-    return combine_host(c, n, m, Q, c_re, c_im, nullptr, 0, nullptr, 0, nullptr, nullptr, out_re, out_im, norm2,
-                        nullptr, nullptr);
+    return combine_host(c, n, 2, m, Q, 2 * n, c_re, c_im, nullptr, 0, nullptr, 0, nullptr, nullptr, out_re, out_im,
+                        norm2, nullptr, nullptr);
 }
 
 int cal_prop_combine_obs(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
@@ -750,8 +732,8 @@ int cal_prop_combine_obs(cal_ctx* c, int64_t n, int m, const double* Q, const do
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine_obs: need n >= 1, 1 <= m <= 512 and non-null arrays");
     if (!obs_counts_ok(nw, W, nphi, phi_re) || (nw + 2 * nphi > 0 && !sums))
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine_obs: need 0 <= nw, nphi <= 4 with their arrays and sums");
-    return combine_host(c, n, m, Q, c_re, c_im, nullptr, nw, W, nphi, phi_re, phi_im, out_re, out_im, norm2, nullptr,
-                        sums);
+    return combine_host(c, n, 2, m, Q, 2 * n, c_re, c_im, nullptr, nw, W, nphi, phi_re, phi_im, out_re, out_im, norm2,
+                        nullptr, sums);
 }
 
 int cal_prop_combine_real_ld(cal_ctx* c, int64_t n, int m, const double* Q, int64_t ldq, const double* a, int nw,
@@ -763,7 +745,8 @@ int cal_prop_combine_real_ld(cal_ctx* c, int64_t n, int m, const double* Q, int6
                          "cal_prop_combine_real: need n >= 1, 1 <= m <= 512, ldq >= n and non-null arrays");
     if (nw < 0 || nw > kPropMaxObs || (nw > 0 && (!W || !sums)))
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine_real: need 0 <= nw <= 4 with W and sums");
-    return combine_real_host(c, n, m, Q, ldq, a, nw, W, out, norm2, sums);
+    return combine_host(c, n, 1, m, Q, ldq, a, nullptr, nullptr, nw, W, 0, nullptr, nullptr, out, nullptr, norm2,
+                        nullptr, sums);
 }
 
 int cal_prop_combine_real(cal_ctx* c, int64_t n, int m, const double* Q, const double* a, int nw, const double* W,
@@ -808,16 +791,9 @@ int cal_prop_set_observables(cal_ctx* c, int nw, const double* W, int nphi, cons
 
 int cal_prop_get_observables(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows, int* ncols) {
     CAL_TRY(active_prop(c, "cal_prop_get_observables", false));
-    const PropState& P = *c->prop;
-    const int nc = 3 + P.nq();
-    const int64_t nr = (int64_t)(P.hist.size() / nc);
-    if (nrows) *nrows = nr;
+    const int nc = 3 + c->prop->nq();
     if (ncols) *ncols = nc;
-    if (!out) return 0;
-    if (first < 0 || count < 0 || first + count > nr)
-        return set_error(c, CAL_ERR_ARG, "cal_prop_get_observables: rows [first, first + count) out of range");
-    std::memcpy(out, P.hist.data() + (size_t)first * nc, (size_t)count * nc * sizeof(double));
-    return 0;
+    return history_rows(c, "cal_prop_get_observables", c->prop->hist, nc, first, count, out, nrows);
 }
 
 int cal_prop_combine_masked(cal_ctx* c, int64_t n, int m, const double* Q, const double* c_re, const double* c_im,
@@ -833,8 +809,8 @@ int cal_prop_combine_masked(cal_ctx* c, int64_t n, int m, const double* Q, const
                          "cal_prop_combine_masked: need 0 <= nw, nphi <= 4 with their arrays and sums");
     if (!mask_ok(mask, n))
         return set_error(c, CAL_ERR_ARG, "cal_prop_combine_masked: the mask must be finite and within [0, 1]");
-    return combine_host(c, n, m, Q, c_re, c_im, mask, nw, W, nphi, phi_re, phi_im, out_re, out_im, norm2, absorbed,
-                        sums);
+    return combine_host(c, n, 2, m, Q, 2 * n, c_re, c_im, mask, nw, W, nphi, phi_re, phi_im, out_re, out_im, norm2,
+                        absorbed, sums);
 }
 
 int cal_prop_set_absorber(cal_ctx* c, const double* mask) {
@@ -869,14 +845,7 @@ int cal_prop_set_absorber(cal_ctx* c, const double* mask) {
 
 int cal_prop_get_absorbed(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows) {
     CAL_TRY(active_prop(c, "cal_prop_get_absorbed", false));
-    const PropState& P = *c->prop;
-    const int64_t nr = (int64_t)(P.ahist.size() / 2);
-    if (nrows) *nrows = nr;
-    if (!out) return 0;
-    if (first < 0 || count < 0 || first + count > nr)
-        return set_error(c, CAL_ERR_ARG, "cal_prop_get_absorbed: rows [first, first + count) out of range");
-    std::memcpy(out, P.ahist.data() + (size_t)first * 2, (size_t)count * 2 * sizeof(double));
-    return 0;
+    return history_rows(c, "cal_prop_get_absorbed", c->prop->ahist, 2, first, count, out, nrows);
 }
 
 // halves = 1: the real-state path (psi_im unused)
@@ -970,23 +939,16 @@ int cal_prop_set_imaginary_time(cal_ctx* c, int on) {
 int cal_prop_get_energetics(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows) {
     if (!c) return CAL_ERR_ARG;
     CAL_TRY(active_prop(c, "cal_prop_get_energetics", false));
-    const PropState& P = *c->prop;
-    const int64_t nr = (int64_t)(P.ehist.size() / 5);
-    if (nrows) *nrows = nr;
-    if (!out) return 0;
-    if (first < 0 || count < 0 || first + count > nr)
-        return set_error(c, CAL_ERR_ARG, "cal_prop_get_energetics: rows [first, first + count) out of range");
-    std::memcpy(out, P.ehist.data() + (size_t)first * 5, (size_t)count * 5 * sizeof(double));
-    return 0;
+    return history_rows(c, "cal_prop_get_energetics", c->prop->ehist, 5, first, count, out, nrows);
 }
 
 // nsteps time steps; f non-null: before step `it` the diagonal is set to
-// V0 + sum_k f[it ldf + k] W_k (one k_diag_drive launch, enqueued ahead of the
-// step's first kernel on the same stream).  With a nonlinear term on, that
-// launch is k_diag_density's instead (the drive and g |psi|^2 together, once
-// per Krylov build: twice per step under "midpoint"), and it runs for f null
-// too, with the amplitudes of the most recent driven step (f_last; zeros
-// before the first)
+// V0 + sum_k f[it ldf + k] W_k (one k_diag_density launch without a state,
+// enqueued ahead of the step's first kernel on the same stream).  With a
+// nonlinear term on, that launch takes the state too (the drive and g |psi|^2
+// together, once per Krylov build: twice per step under "midpoint"), and it
+// runs for f null too, with the amplitudes of the most recent driven step
+// (f_last; zeros before the first)
 static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int adaptive, int nsteps, const double* f,
                       int ldf) {
     const std::string w = who;
@@ -1014,8 +976,8 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
         if (f)
             for (int k = 0; k < P.nk; ++k) P.f_last[k] = f[(size_t)it * ldf + k];
         const double nrm2_n = P.nrm2;  // psi_n's: the energetics row's N_n
-        int kuse = 0;
-        double resid = 0.0, scale = 0.0;
+        int ks = 0;
+        double resid = 0.0;
         double en[2] = {0.0, 0.0};  // mu_n and res_n, from the step's first build
         if (P.nl_on()) {
             // the drive and the density of psi_n in one launch; "midpoint" then
@@ -1024,40 +986,22 @@ static int prop_steps(cal_ctx* c, const char* who, double dt, double tol, int ad
             status = density_dev(c, P, P.f_last, P.g, nullptr, 0.0);
             if (status < 0) break;
             if (P.nl_mid) {
-                status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid, &scale, en);
-                if (status < 0) break;
-                if (kuse == 0) {  // the state is unchanged
-                    status = set_error(c, CAL_WARN_BREAKDOWN, w + ": the predictor's first CA block broke down");
-                    break;
-                }
-                const int kp = kuse * P.s;
-                for (int j = 0; j < kp; ++j) {
-                    cre[j] = scale * cre[j];
-                    cim[j] = scale * cim[j];
-                }
+                status = krylov_scaled(c, P, dt, tol, adaptive, w + ": the predictor's first CA block broke down", &ks,
+                                       cre, cim, &resid, en);
+                if (status != 0) break;
                 const LanczosView vp = lanczos_view(c);
-                status = combine_predict_dev(c, P, vp.Q, vp.ld, kp, cre.data(), cim.data());
+                status = combine_dev(c, P, vp.Q, vp.ld, ks, cre.data(), cim.data(), true);
                 if (status < 0) break;
                 status = density_dev(c, P, P.f_last, 0.5 * P.g, P.d_psi2 + c->A.lpad, 0.5 * P.g);
                 if (status < 0) break;
-                kuse = 0;
             }
         } else if (f) {
             status = diag_update_dev(c, P.d_v0, P.n, P.halves, P.nk, P.d_drv, P.ldd, f + (size_t)it * ldf);
             if (status < 0) break;
         }
-        status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid, &scale,
-                        P.nl_on() && P.nl_mid ? nullptr : en);
-        if (status < 0) break;
-        if (kuse == 0) {  // the state is unchanged
-            status = set_error(c, CAL_WARN_BREAKDOWN, w + ": the first CA block broke down");
-            break;
-        }
-        const int ks = kuse * P.s;
-        for (int j = 0; j < ks; ++j) {  // nrm * c (imaginary time: sqrt(N0) c / ||c||)
-            cre[j] = scale * cre[j];
-            cim[j] = scale * cim[j];
-        }
+        status = krylov_scaled(c, P, dt, tol, adaptive, w + ": the first CA block broke down", &ks, cre, cim, &resid,
+                               P.nl_on() && P.nl_mid ? nullptr : en);
+        if (status != 0) break;
         const LanczosView v = lanczos_view(c);
         status = combine_dev(c, P, v.Q, v.ld, ks, cre.data(), cim.data());
         if (status < 0) break;
@@ -1180,14 +1124,7 @@ int cal_prop_set_nonlinear(cal_ctx* c, double g, const char* density) {
 int cal_prop_get_nonlinear(cal_ctx* c, int64_t first, int64_t count, double* out, int64_t* nrows) {
     if (!c) return CAL_ERR_ARG;
     CAL_TRY(active_prop(c, "cal_prop_get_nonlinear", false));
-    const PropState& P = *c->prop;
-    const int64_t nr = (int64_t)(P.nhist.size() / 2);
-    if (nrows) *nrows = nr;
-    if (!out) return 0;
-    if (first < 0 || count < 0 || first + count > nr)
-        return set_error(c, CAL_ERR_ARG, "cal_prop_get_nonlinear: rows [first, first + count) out of range");
-    std::memcpy(out, P.nhist.data() + (size_t)first * 2, (size_t)count * 2 * sizeof(double));
-    return 0;
+    return history_rows(c, "cal_prop_get_nonlinear", c->prop->nhist, 2, first, count, out, nrows);
 }
 
 int cal_prop_refresh_shifts(cal_ctx* c) {
@@ -1234,14 +1171,11 @@ int cal_ca_lanczos_prop(cal_ctx* c, int64_t n, const double* r_re, const double*
     CAL_TRY(cal_prop_begin(c, n, r_re, r_im, s, m, basis, eigest, neig));
     PropState& P = *c->prop;
     std::vector<double> cre, cim;
-    int kuse = 0;
+    int ks = 0;
     double resid = 0.0;
-    double scale = 0.0;
-    int status = krylov(c, P, dt, tol, adaptive, &kuse, cre, cim, &resid, &scale, nullptr);
-    if (status >= 0 && kuse == 0)
-        status = set_error(c, CAL_WARN_BREAKDOWN, "cal_ca_lanczos_prop: the first CA block broke down");
+    int status = krylov_scaled(c, P, dt, tol, adaptive, "cal_ca_lanczos_prop: the first CA block broke down", &ks, cre,
+                               cim, &resid, nullptr);
     if (status == 0) {
-        const int ks = kuse * s;
         const LanczosView v = lanczos_view(c);
         *lsteps = ks;
         for (int j = 0; j < ks; ++j)

@@ -22,8 +22,8 @@
 // order): launch_reduce turns them into the next step's squared norm without
 // another sweep, deterministically (no atomics).
 //
-// launch_prop_combine is the one host entry: it picks OBS and ABS from what
-// its PropCombine carries and VT / VB from the alignment of Q and out.
+// launch_prop_combine is the one host entry: it picks OBS, ABS and REAL from
+// what its PropCombine carries and VT / VB from the alignment of Q and out.
 //
 // OBS = true (nw + np > 0) also reduces observables of the new
 // state in the same sweep: nw real diagonal operators W_k and np reference
@@ -55,6 +55,16 @@
 // by pair, then the nrm chain's wave tree and wave order; its block partial is
 // quantity 1 + nw + 2 np (after the observables; 1 without OBS).  ABS = false
 // is the kernel as it was: the mask is an `if constexpr` away.
+//
+// REAL = true is the combine of a real state (cal_prop_begin_real; an
+// imaginary-time step keeps a real state real), out[i] = sum_j Q[i,j] a_j for
+// i in [0, n): the same kernel without the lower half -- no loads of it, no b,
+// no sb in LDS, VB unused, no mask and no reference states.  Staging, the rows
+// per lane and per block, the odd-n tail, the wave sums and the epilogue are
+// the ones above; the per-row chains are t = t + x*a_j, then nrm = nrm + t*t
+// and with OBS, for k < nw,  d = t*t;  accW[k] = accW[k] + w*d  (no b term, not
+// even a zero one).  (n m + n + n nw) 8 bytes.  The stacked instantiations keep
+// the statement order they had: the scheduler follows it.
 #include "cal_internal.hpp"
 
 namespace cal {
@@ -142,8 +152,9 @@ __device__ __forceinline__ void mask_row(double m, double& t, double& b, double&
     b = m * b;
 }
 
-// the observables' terms of the adjacent rows r, r + 1 (PAIR) or of row r alone
-template <bool PAIR>
+// the observables' terms of the adjacent rows r, r + 1 (PAIR) or of row r alone;
+// REAL: d = t*t with no b term, and no reference states
+template <bool PAIR, bool REAL>
 __device__ __forceinline__ void obs_rows(const PropObs& o, int64_t r, double t0, double t1, double b0, double b1,
                                          PropObsAcc& s) {
 #pragma unroll
@@ -154,14 +165,15 @@ __device__ __forceinline__ void obs_rows(const PropObs& o, int64_t r, double t0,
             if (PAIR) load2<true>(w, w0, w1);
             else w0 = *w;
             double d = t0 * t0;
-            d = d + b0 * b0;
+            if constexpr (!REAL) d = d + b0 * b0;
             s.w[k] = s.w[k] + w0 * d;
             if (PAIR) {
                 d = t1 * t1;
-                d = d + b1 * b1;
+                if constexpr (!REAL) d = d + b1 * b1;
                 s.w[k] = s.w[k] + w1 * d;
             }
         }
+    if constexpr (REAL) return;
 #pragma unroll
     for (int k = 0; k < kPropMaxObs; ++k)
         if (k < o.np) {
@@ -188,14 +200,15 @@ __device__ __forceinline__ void obs_rows(const PropObs& o, int64_t r, double t0,
         }
 }
 
-template <bool VT, bool VB, bool OBS, bool ABS>
+template <bool VT, bool VB, bool OBS, bool ABS, bool REAL>
 __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __restrict__ Q, int64_t ld, int64_t n,
                                                                int m, const double* __restrict__ a,
                                                                const double* __restrict__ b,
                                                                double* __restrict__ out,
                                                                double* __restrict__ partial, PropObsArg<OBS, ABS> obs) {
+    static_assert(!REAL || (!VB && !ABS), "a real state has no lower half and takes no mask");
     __shared__ double sa[kPropMaxCols];
-    __shared__ double sb[kPropMaxCols];
+    __shared__ double sb[kPropMaxCols];  // REAL: no statement names it, so it takes no LDS
     __shared__ double ws[kPropThreads / 64];
     PropObsAcc acc;
     if constexpr (OBS) {
@@ -204,7 +217,7 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
     }
     for (int j = threadIdx.x; j < m; j += kPropThreads) {
         sa[j] = a[j];
-        sb[j] = b[j];
+        if constexpr (!REAL) sb[j] = b[j];
     }
     __syncthreads();
 
@@ -216,24 +229,27 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
         const int64_t r = base + 2 * ((int64_t)p * kPropThreads + threadIdx.x);
         if (r + 1 < n) {
             const double* qt = Q + r;
-            const double* qb = Q + n + r;
+            const double* qb = REAL ? nullptr : Q + n + r;  // a real state has no lower half
             double t0 = 0.0, t1 = 0.0, b0 = 0.0, b1 = 0.0;
 #pragma unroll 4
             for (int j = 0; j < m; ++j) {
-                double xt0, xt1, xb0, xb1;
+                double xt0, xt1, xb0, xb1, bj;  // REAL: the lower half and b are never read
                 load2<VT>(qt, xt0, xt1);
-                load2<VB>(qb, xb0, xb1);
+                if constexpr (!REAL) load2<VB>(qb, xb0, xb1);
                 qt += ld;
-                qb += ld;
-                const double aj = sa[j], bj = sb[j];
+                if constexpr (!REAL) qb += ld;
+                const double aj = sa[j];
+                if constexpr (!REAL) bj = sb[j];
                 t0 = t0 + xt0 * aj;
                 t1 = t1 + xt1 * aj;
-                t0 = t0 - xb0 * bj;
-                t1 = t1 - xb1 * bj;
-                b0 = b0 + xt0 * bj;
-                b1 = b1 + xt1 * bj;
-                b0 = b0 + xb0 * aj;
-                b1 = b1 + xb1 * aj;
+                if constexpr (!REAL) {
+                    t0 = t0 - xb0 * bj;
+                    t1 = t1 - xb1 * bj;
+                    b0 = b0 + xt0 * bj;
+                    b1 = b1 + xt1 * bj;
+                    b0 = b0 + xb0 * aj;
+                    b1 = b1 + xb1 * aj;
+                }
             }
             if constexpr (ABS) {
                 double m0, m1;
@@ -242,32 +258,39 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
                 mask_row(m1, t1, b1, absd);
             }
             store2<VT>(out + r, t0, t1);
-            store2<VB>(out + n + r, b0, b1);
+            if constexpr (!REAL) store2<VB>(out + n + r, b0, b1);
             nrm = nrm + t0 * t0;
             nrm = nrm + t1 * t1;
-            nrm = nrm + b0 * b0;
-            nrm = nrm + b1 * b1;
-            if constexpr (OBS) obs_rows<true>(obs.o, r, t0, t1, b0, b1, acc);
+            if constexpr (!REAL) {
+                nrm = nrm + b0 * b0;
+                nrm = nrm + b1 * b1;
+            }
+            if constexpr (OBS) obs_rows<true, REAL>(obs.o, r, t0, t1, b0, b1, acc);
         } else if (r < n) {  // the last row of an odd n
             const double* qt = Q + r;
-            const double* qb = Q + n + r;
+            const double* qb = REAL ? nullptr : Q + n + r;  // a real state has no lower half
             double t0 = 0.0, b0 = 0.0;
             for (int j = 0; j < m; ++j) {
-                const double xt0 = *qt, xb0 = *qb;
+                double xb0, bj;
+                const double xt0 = *qt;
+                if constexpr (!REAL) xb0 = *qb;
                 qt += ld;
-                qb += ld;
-                const double aj = sa[j], bj = sb[j];
+                if constexpr (!REAL) qb += ld;
+                const double aj = sa[j];
+                if constexpr (!REAL) bj = sb[j];
                 t0 = t0 + xt0 * aj;
-                t0 = t0 - xb0 * bj;
-                b0 = b0 + xt0 * bj;
-                b0 = b0 + xb0 * aj;
+                if constexpr (!REAL) {
+                    t0 = t0 - xb0 * bj;
+                    b0 = b0 + xt0 * bj;
+                    b0 = b0 + xb0 * aj;
+                }
             }
             if constexpr (ABS) mask_row(obs.mask[r], t0, b0, absd);
             out[r] = t0;
-            out[n + r] = b0;
+            if constexpr (!REAL) out[n + r] = b0;
             nrm = nrm + t0 * t0;
-            nrm = nrm + b0 * b0;
-            if constexpr (OBS) obs_rows<false>(obs.o, r, t0, 0.0, b0, 0.0, acc);
+            if constexpr (!REAL) nrm = nrm + b0 * b0;
+            if constexpr (OBS) obs_rows<false, REAL>(obs.o, r, t0, 0.0, b0, 0.0, acc);
         }
     }
     nrm = prop_wave_sum(nrm);
@@ -275,7 +298,7 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
     if (lane == 0) ws[wave] = nrm;
     if constexpr (OBS) {
         double(*wo)[kPropThreads / 64] = obs_wave_sums();
-        const int nw = obs.o.nw, np = obs.o.np;
+        const int nw = obs.o.nw, np = REAL ? 0 : obs.o.np;
 #pragma unroll
         for (int k = 0; k < kPropMaxObs; ++k)
             if (k < nw) {
@@ -302,7 +325,7 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
     if constexpr (OBS) {  // thread q writes quantity q of this block
         double(*wo)[kPropThreads / 64] = obs_wave_sums();
         const int q = (int)threadIdx.x - 1;
-        if (q >= 0 && q < obs.o.nw + 2 * obs.o.np)
+        if (q >= 0 && q < obs.o.nw + 2 * (REAL ? 0 : obs.o.np))
             partial[(int64_t)(q + 1) * gridDim.x + blockIdx.x] = ((wo[q][0] + wo[q][1]) + wo[q][2]) + wo[q][3];
     }
     if constexpr (ABS) {  // after the observables: quantity 1 + nw + 2 np
@@ -310,107 +333,6 @@ __global__ __launch_bounds__(kPropThreads) void k_prop_combine(const double* __r
         int q = 1;
         if constexpr (OBS) q = 1 + obs.o.nw + 2 * obs.o.np;
         if (threadIdx.x == 0) partial[(int64_t)q * gridDim.x + blockIdx.x] = ((wa[0] + wa[1]) + wa[2]) + wa[3];
-    }
-}
-
-// k_prop_combine_real: the combine of a real state (cal_prop_begin_real; an
-// imaginary-time step keeps a real state real), out[i] = sum_j Q[i,j] a_j for
-// i in [0, n) -- k_prop_combine without the lower half: the same rows per lane
-// and per block, a staged in LDS, 16-byte accesses when V (the origins of Q and
-// out 16-byte aligned, ld even), 8-byte ones otherwise and for the last row of
-// an odd n.  Per row: t = +0.0; j ascending: t = t + x*a_j; then, a lane's rows
-// in row order, nrm = nrm + t*t and with OBS, for k < nw,
-//   d = t*t;  accW[k] = accW[k] + w*d
-// reduced as k_prop_combine reduces (wave tree, the four waves in order,
-// quantity q's block share at partial[q * gridDim.x + block]: q = 0 the squared
-// norm, 1 + k <W_k>).  (n m + n + n nw) 8 bytes; vector stores only.
-template <bool V, bool OBS>
-__global__ __launch_bounds__(kPropThreads) void k_prop_combine_real(const double* __restrict__ Q, int64_t ld,
-                                                                    int64_t n, int m, const double* __restrict__ a,
-                                                                    double* __restrict__ out,
-                                                                    double* __restrict__ partial,
-                                                                    PropObsArg<OBS, false> obs) {
-    __shared__ double sa[kPropMaxCols];
-    __shared__ double ws[kPropThreads / 64];
-    double accw[kPropMaxObs];
-    if constexpr (OBS) {
-#pragma unroll
-        for (int k = 0; k < kPropMaxObs; ++k) accw[k] = 0.0;
-    }
-    for (int j = threadIdx.x; j < m; j += kPropThreads) sa[j] = a[j];
-    __syncthreads();
-
-    const int64_t base = (int64_t)blockIdx.x * kPropBlockRows;
-    double nrm = 0.0;
-#pragma unroll
-    for (int p = 0; p < kPropPairs; ++p) {
-        const int64_t r = base + 2 * ((int64_t)p * kPropThreads + threadIdx.x);
-        if (r + 1 < n) {
-            const double* q = Q + r;
-            double t0 = 0.0, t1 = 0.0;
-#pragma unroll 4
-            for (int j = 0; j < m; ++j) {
-                double x0, x1;
-                load2<V>(q, x0, x1);
-                q += ld;
-                const double aj = sa[j];
-                t0 = t0 + x0 * aj;
-                t1 = t1 + x1 * aj;
-            }
-            store2<V>(out + r, t0, t1);
-            nrm = nrm + t0 * t0;
-            nrm = nrm + t1 * t1;
-            if constexpr (OBS) {
-#pragma unroll
-                for (int k = 0; k < kPropMaxObs; ++k)
-                    if (k < obs.o.nw) {
-                        double w0, w1;
-                        load2<true>(obs.o.W + k * obs.o.ld + r, w0, w1);
-                        double d = t0 * t0;
-                        accw[k] = accw[k] + w0 * d;
-                        d = t1 * t1;
-                        accw[k] = accw[k] + w1 * d;
-                    }
-            }
-        } else if (r < n) {  // the last row of an odd n
-            const double* q = Q + r;
-            double t0 = 0.0;
-            for (int j = 0; j < m; ++j) {
-                const double x0 = *q;
-                q += ld;
-                t0 = t0 + x0 * sa[j];
-            }
-            out[r] = t0;
-            nrm = nrm + t0 * t0;
-            if constexpr (OBS) {
-#pragma unroll
-                for (int k = 0; k < kPropMaxObs; ++k)
-                    if (k < obs.o.nw) {
-                        const double d = t0 * t0;
-                        accw[k] = accw[k] + obs.o.W[k * obs.o.ld + r] * d;
-                    }
-            }
-        }
-    }
-    nrm = prop_wave_sum(nrm);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) ws[wave] = nrm;
-    if constexpr (OBS) {
-        double(*wo)[kPropThreads / 64] = obs_wave_sums();
-#pragma unroll
-        for (int k = 0; k < kPropMaxObs; ++k)
-            if (k < obs.o.nw) {
-                const double v = prop_wave_sum(accw[k]);
-                if (lane == 0) wo[k][wave] = v;
-            }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
-    if constexpr (OBS) {  // thread q writes quantity q of this block
-        double(*wo)[kPropThreads / 64] = obs_wave_sums();
-        const int q = (int)threadIdx.x - 1;
-        if (q >= 0 && q < obs.o.nw)
-            partial[(int64_t)(q + 1) * gridDim.x + blockIdx.x] = ((wo[q][0] + wo[q][1]) + wo[q][2]) + wo[q][3];
     }
 }
 
@@ -426,20 +348,26 @@ int prop_combine_blocks(int64_t n) {
 int prop_combine_quantities(const PropCombine& p) { return 1 + p.obs.nw + 2 * p.obs.np + (p.mask ? 1 : 0); }
 
 // the VT / VB choice: a half takes 16-byte accesses when its rows of every
-// column and of the output start 16-byte aligned (even leading dimension)
-template <bool OBS, bool ABS>
+// column and of the output start 16-byte aligned (even leading dimension);
+// a real state (REAL) is the upper half alone, VB unused
+template <bool OBS, bool ABS, bool REAL = false>
 static hipError_t launch_combine(const PropCombine& p, PropObsArg<OBS, ABS> obs, hipStream_t st) {
     const dim3 grid((unsigned)prop_combine_blocks(p.n)), block(kPropThreads);
     const bool even = (p.ld & 1) == 0;
     const bool vt = even && aligned16(p.Q) && aligned16(p.out);
-    const bool vb = even && aligned16(p.Q + p.n) && aligned16(p.out + p.n);
     auto launch = [&](auto k) {
         hipLaunchKernelGGL(k, grid, block, 0, st, p.Q, p.ld, p.n, p.m, p.a, p.b, p.out, p.partial, obs);
     };
-    if (vt && vb) launch(k_prop_combine<true, true, OBS, ABS>);
-    else if (vt) launch(k_prop_combine<true, false, OBS, ABS>);
-    else if (vb) launch(k_prop_combine<false, true, OBS, ABS>);
-    else launch(k_prop_combine<false, false, OBS, ABS>);
+    if constexpr (REAL) {
+        if (vt) launch(k_prop_combine<true, false, OBS, ABS, true>);
+        else launch(k_prop_combine<false, false, OBS, ABS, true>);
+    } else {
+        const bool vb = even && aligned16(p.Q + p.n) && aligned16(p.out + p.n);
+        if (vt && vb) launch(k_prop_combine<true, true, OBS, ABS, false>);
+        else if (vt) launch(k_prop_combine<true, false, OBS, ABS, false>);
+        else if (vb) launch(k_prop_combine<false, true, OBS, ABS, false>);
+        else launch(k_prop_combine<false, false, OBS, ABS, false>);
+    }
     return hipGetLastError();
 }
 
@@ -453,26 +381,14 @@ static bool obs_arg_ok(const PropObs& o, int64_t n) {
     return true;
 }
 
-// the real state's sweep: one half, V from the alignment of Q and out
-template <bool OBS>
-static hipError_t launch_combine_real(const PropCombine& p, PropObsArg<OBS, false> obs, hipStream_t st) {
-    const dim3 grid((unsigned)prop_combine_blocks(p.n)), block(kPropThreads);
-    auto launch = [&](auto k) {
-        hipLaunchKernelGGL(k, grid, block, 0, st, p.Q, p.ld, p.n, p.m, p.a, p.out, p.partial, obs);
-    };
-    if ((p.ld & 1) == 0 && aligned16(p.Q) && aligned16(p.out)) launch(k_prop_combine_real<true, OBS>);
-    else launch(k_prop_combine_real<false, OBS>);
-    return hipGetLastError();
-}
-
 hipError_t launch_prop_combine(const PropCombine& p, hipStream_t st) {
     if (p.n < 1 || p.m < 1 || p.m > kPropMaxCols || p.ld < (p.real ? 1 : 2) * p.n) return hipErrorInvalidValue;
     if (p.n > ((int64_t)1 << 40)) return hipErrorInvalidValue;
     if (!obs_arg_ok(p.obs, p.n)) return hipErrorInvalidValue;
     if (p.real) {  // no reference states and no mask on a real state
         if (p.obs.np > 0 || p.mask) return hipErrorInvalidValue;
-        if (p.obs.nw > 0) return launch_combine_real(p, PropObsArg<true, false>{p.obs}, st);
-        return launch_combine_real(p, PropObsArg<false, false>{}, st);
+        if (p.obs.nw > 0) return launch_combine<true, false, true>(p, PropObsArg<true, false>{p.obs}, st);
+        return launch_combine<false, false, true>(p, PropObsArg<false, false>{}, st);
     }
     // the mask's 16-byte loads: the rules of the observables' columns
     if (p.mask && (!aligned16(p.mask) || p.ldm < p.n || (p.ldm & 1) != 0)) return hipErrorInvalidValue;
@@ -494,12 +410,13 @@ hipError_t launch_prop_combine(const PropCombine& p, hipStream_t st) {
 // small integers in doubles; wave tree, the four waves in order) so that
 // launch_reduce gives the two totals in the fixed order, no atomics.
 //
-// k_diag_drive (once per time step) is one row per lane with 8-byte accesses:
+// k_diag_density (once per Krylov build) is one row per lane with 8-byte accesses:
 //   d = V0[i];  k ascending:  p = f_k * W_k[i];  d = d + p
 // product and sum rounded separately (-ffp-contract=off), the amplitudes
 // kernel arguments (wave-uniform) and the loop unrolled to the cap with
 // uniform guards, as the OBS combine's; then the same d goes to the row's
-// slot of either half.  Vector stores only.
+// slot of either half.  Vector stores only.  The chain and the stores are
+// written once; the template's state count adds the nonlinear term.
 namespace {
 
 constexpr int kDiagThreads = 256;
@@ -537,53 +454,36 @@ __global__ __launch_bounds__(kDiagThreads) void k_diag_find(const int* __restric
     }
 }
 
-template <bool SPLIT>
-__global__ __launch_bounds__(kDiagThreads) void k_diag_drive(DiagDrive a) {
-    const int64_t i = (int64_t)blockIdx.x * kDiagThreads + threadIdx.x;
-    if (i >= a.n) return;
-    double d = a.V0[i];
-#pragma unroll
-    for (int k = 0; k < kDriveMaxOps; ++k)
-        if (k < a.nk) {
-            const double p = a.f[k] * a.W[k * a.ldw + i];
-            d = d + p;
-        }
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-        if (h < a.halves) {
-            const int64_t r = i + h * a.n;
-            a.val[a.dpos[r]] = d;
-            if (SPLIT) a.ds_diag[r] = d;
-        }
-}
-
-// k_diag_density: k_diag_drive with the nonlinear term g |psi|^2 of one state
-// (TWO = false) or of two (TWO = true: the midpoint rule's average of the
-// densities of psi_n and the predicted psi*).  One row per lane, 8-byte
-// accesses only (the lower half of a state starts at row n, which may be odd),
-// the order of cal_internal.hpp's DiagDensity:
+// NS: the states whose density g |psi|^2 joins the diagonal.  0: the drive
+// alone -- no state load, no q, no LDS, no barrier, partial untouched (null is
+// allowed).  1: the nonlinear term of one state A; 2: of two (the midpoint
+// rule's average of the densities of psi_n and the predicted psi*), the order
+// of cal_internal.hpp's DiagDrive:
 //   ra = ua*ua;  ra = ra + va*va;  [rb likewise]  the drive's chain into d;
-//   p = ga*ra;  d = d + p;  [p = gb*rb;  d = d + p]  the drive's stores
+//   p = ga*ra;  d = d + p;  [p = gb*rb;  d = d + p]  the stores
 // and the lane's q = ra*ra (0 past row n) summed as everything else here:
-// wave tree, the four waves in order, one partial per block.  No lane leaves
-// before the barrier.  REAL: the states are real vectors of n rows
+// wave tree, the four waves in order, one partial per block; no lane leaves
+// before the barrier.  The lower half of a state starts at row n, which may be
+// odd: 8-byte accesses.  REAL: the states are real vectors of n rows
 // (cal_prop_begin_real), there is no lower half to load -- ra = ua*ua, rb =
 // ub*ub -- and halves is 1; everything else is the same.
-template <bool SPLIT, bool TWO, bool REAL = false>
-__global__ __launch_bounds__(kDiagThreads) void k_diag_density(DiagDensity a) {
-    __shared__ double ws[kDiagThreads / 64];
-    const int64_t n = a.d.n;
+template <bool SPLIT, int NS, bool REAL>
+__global__ __launch_bounds__(kDiagThreads) void k_diag_density(DiagDrive a) {
+    static_assert(NS >= 0 && NS <= 2 && (NS > 0 || !REAL), "REAL describes the states");
+    const int64_t n = a.n;
     const int64_t i = (int64_t)blockIdx.x * kDiagThreads + threadIdx.x;
     double acc = 0.0;
     if (i < n) {
-        const double ua = a.A[i];
-        double ra = ua * ua;
-        if constexpr (!REAL) {
-            const double va = a.A[n + i];
-            ra = ra + va * va;
+        double ra = 0.0, rb = 0.0;
+        if constexpr (NS >= 1) {
+            const double ua = a.A[i];
+            ra = ua * ua;
+            if constexpr (!REAL) {
+                const double va = a.A[n + i];
+                ra = ra + va * va;
+            }
         }
-        double rb = 0.0;
-        if (TWO) {
+        if constexpr (NS == 2) {
             const double ub = a.B[i];
             rb = ub * ub;
             if constexpr (!REAL) {
@@ -591,34 +491,41 @@ __global__ __launch_bounds__(kDiagThreads) void k_diag_density(DiagDensity a) {
                 rb = rb + vb * vb;
             }
         }
-        double d = a.d.V0[i];
+        double d = a.V0[i];
 #pragma unroll
         for (int k = 0; k < kDriveMaxOps; ++k)
-            if (k < a.d.nk) {
-                const double p = a.d.f[k] * a.d.W[k * a.d.ldw + i];
+            if (k < a.nk) {
+                const double p = a.f[k] * a.W[k * a.ldw + i];
                 d = d + p;
             }
-        double p = a.ga * ra;
-        d = d + p;
-        if (TWO) {
-            p = a.gb * rb;
+        if constexpr (NS >= 1) {
+            const double p = a.ga * ra;
+            d = d + p;
+        }
+        if constexpr (NS == 2) {
+            const double p = a.gb * rb;
             d = d + p;
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h)
-            if (h < a.d.halves) {
+            if (h < a.halves) {
                 const int64_t r = i + h * n;
-                a.d.val[a.d.dpos[r]] = d;
-                if (SPLIT) a.d.ds_diag[r] = d;
+                a.val[a.dpos[r]] = d;
+                if (SPLIT) a.ds_diag[r] = d;
             }
-        const double q = ra * ra;
-        acc = acc + q;
+        if constexpr (NS >= 1) {
+            const double q = ra * ra;
+            acc = acc + q;
+        }
     }
-    acc = prop_wave_sum(acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) ws[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) a.partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+    if constexpr (NS >= 1) {
+        __shared__ double ws[kDiagThreads / 64];
+        acc = prop_wave_sum(acc);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) ws[wave] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) a.partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+    }
 }
 
 }  // namespace
@@ -636,45 +543,29 @@ hipError_t launch_diag_find(const int* rowptr, const int* col, int64_t n, int* d
     return hipGetLastError();
 }
 
-hipError_t launch_diag_drive(const DiagDrive& a, hipStream_t st) {
-    if (a.n < 1 || a.n >= ((int64_t)1 << 31) || a.halves < 1 || a.halves > 2 || a.nk < 0 || a.nk > kDriveMaxOps)
-        return hipErrorInvalidValue;
-    if (!a.V0 || !a.dpos || !a.val || (a.nk > 0 && (!a.W || a.ldw < a.n))) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.n + kDiagThreads - 1) / kDiagThreads)), block(kDiagThreads);
-    if (a.ds_diag) hipLaunchKernelGGL(k_diag_drive<true>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(k_diag_drive<false>, grid, block, 0, st, a);
-    return hipGetLastError();
-}
-
 int diag_density_blocks(int64_t n) {
     const int64_t b = (n + kDiagThreads - 1) / kDiagThreads;
     return (int)(b < 1 ? 1 : b);
 }
 
-hipError_t launch_diag_density(const DiagDensity& a, hipStream_t st) {
-    const DiagDrive& d = a.d;
-    if (d.n < 1 || d.n >= ((int64_t)1 << 31) || d.halves < 1 || d.halves > 2 || d.nk < 0 || d.nk > kDriveMaxOps)
+hipError_t launch_diag_density(const DiagDrive& a, hipStream_t st) {
+    if (a.n < 1 || a.n >= ((int64_t)1 << 31) || a.halves < 1 || a.halves > 2 || a.nk < 0 || a.nk > kDriveMaxOps)
         return hipErrorInvalidValue;
-    if (!d.V0 || !d.dpos || !d.val || (d.nk > 0 && (!d.W || d.ldw < d.n))) return hipErrorInvalidValue;
-    if (!a.A || !a.partial) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)diag_density_blocks(d.n)), block(kDiagThreads);
+    if (!a.V0 || !a.dpos || !a.val || (a.nk > 0 && (!a.W || a.ldw < a.n))) return hipErrorInvalidValue;
+    // a state brings its partials; real states are written on one half
+    if (a.A ? !a.partial || (a.real && a.halves != 1) : a.B != nullptr) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)diag_density_blocks(a.n)), block(kDiagThreads);
     auto launch = [&](auto k) { hipLaunchKernelGGL(k, grid, block, 0, st, a); };
-    if (a.real) {
-        if (d.halves != 1) return hipErrorInvalidValue;
-        if (d.ds_diag) {
-            if (a.B) launch(k_diag_density<true, true, true>);
-            else launch(k_diag_density<true, false, true>);
-        } else {
-            if (a.B) launch(k_diag_density<false, true, true>);
-            else launch(k_diag_density<false, false, true>);
-        }
-    } else if (d.ds_diag) {
-        if (a.B) launch(k_diag_density<true, true>);
-        else launch(k_diag_density<true, false>);
-    } else {
-        if (a.B) launch(k_diag_density<false, true>);
-        else launch(k_diag_density<false, false>);
-    }
+    auto states = [&](auto split) {
+        constexpr bool S = decltype(split)::value;
+        if (!a.A) launch(k_diag_density<S, 0, false>);
+        else if (a.real && a.B) launch(k_diag_density<S, 2, true>);
+        else if (a.real) launch(k_diag_density<S, 1, true>);
+        else if (a.B) launch(k_diag_density<S, 2, false>);
+        else launch(k_diag_density<S, 1, false>);
+    };
+    if (a.ds_diag) states(std::true_type{});
+    else states(std::false_type{});
     return hipGetLastError();
 }
 

@@ -861,17 +861,8 @@ int diag_positions(cal_ctx* c) {
     return diag_verdict(c);
 }
 
-int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
-                    const double* f) {
-    CAL_TRY(diag_positions(c));
-    DevMatrix& A = c->A;
-    if (halves < 1 || halves > 2 || n < 1 || n * halves != A.n_local || nk < 0 || nk > kDriveMaxOps || !V0_dev ||
-        (nk > 0 && (!W_dev || !f || ldw < n)))
-        return set_error(c, CAL_ERR_ARG, "diag_update_dev: bad arguments");
-    if (A.shared) {  // both halves read one slot: it is written once, on H's rows
-        if (halves != 2) return set_error(c, CAL_ERR_ARG, "diag_update_dev: a shared matrix takes both halves at once");
-        halves = 1;
-    }
+// the drive's half of a DiagDrive, as diag_update_dev and diag_density_dev take it
+static DiagDrive diag_drive_args(const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw) {
     DiagDrive a;
     a.V0 = V0_dev;
     a.W = W_dev;
@@ -879,57 +870,55 @@ int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int
     a.n = n;
     a.nk = nk;
     a.halves = halves;
-    for (int k = 0; k < nk; ++k) a.f[k] = f[k];
+    return a;
+}
+
+// the one routine behind diag_update_dev (a.A null: the drive alone) and
+// diag_density_dev (`state`: the density of a.A, and of a.B when given, with
+// it).  a: the caller's arguments; the amplitudes, the matrix's arrays and the
+// rule for a shared matrix are filled in here
+static int diag_write_dev(cal_ctx* c, const std::string& who, DiagDrive a, const double* f, bool state) {
+    CAL_TRY(diag_positions(c));
+    DevMatrix& A = c->A;
+    const int64_t n = a.n;
+    if (a.halves < 1 || a.halves > 2 || n < 1 || n * a.halves != A.n_local || a.nk < 0 || a.nk > kDriveMaxOps ||
+        !a.V0 || (a.nk > 0 && (!a.W || !f || a.ldw < n)) || (state && (!a.A || !a.partial)))
+        return set_error(c, CAL_ERR_ARG, who + ": bad arguments");
+    a.real = state && a.halves == 1;  // the states are real vectors of n rows
+    if (A.shared) {  // both halves read one slot: it is written once, on H's rows
+        if (a.halves != 2) return set_error(c, CAL_ERR_ARG, who + ": a shared matrix takes both halves at once");
+        a.halves = 1;
+    }
+    for (int k = 0; k < a.nk; ++k) a.f[k] = f[k];
     a.dpos = A.dpos;
     a.val = A.val;
     a.ds_diag = A.use_dsplit ? A.ds_diag : nullptr;
+    if (!a.B) a.gb = 0.0;
     // V0, the nk columns and the positions in; the slots (and the streamed diagonal) out
-    const double bytes = (double)n * (8.0 * (1 + nk) + 4.0 * halves) + (double)n * halves * (A.use_dsplit ? 16.0 : 8.0);
-    const int t = timer_begin(c, 7, bytes);  // a kind of its own: one launch per time step, measured alone
-    const hipError_t e = launch_diag_drive(a, c->stream);
+    double bytes = (double)n * (8.0 * (1 + a.nk) + 4.0 * a.halves) + (double)n * a.halves * (A.use_dsplit ? 16.0 : 8.0);
+    // the 2n (real: n) doubles of each state in; one partial per block out
+    if (state) bytes += (double)n * (a.real ? 8.0 : 16.0) * (a.B ? 2 : 1) + 8.0 * diag_density_blocks(n);
+    const int t = timer_begin(c, 7, bytes);  // a kind of its own: the one launch that rewrites the diagonal
+    const hipError_t e = launch_diag_density(a, c->stream);
     timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_diag_drive");
+    if (e != hipSuccess) return hip_fail(c, e, state ? "launch_diag_density" : "launch_diag_drive");  // as before
     return 0;
+}
+
+int diag_update_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
+                    const double* f) {
+    return diag_write_dev(c, "diag_update_dev", diag_drive_args(V0_dev, n, halves, nk, W_dev, ldw), f, false);
 }
 
 int diag_density_dev(cal_ctx* c, const double* V0_dev, int64_t n, int halves, int nk, const double* W_dev, int64_t ldw,
                      const double* f, const double* A_dev, double ga, const double* B_dev, double gb, double* partial) {
-    CAL_TRY(diag_positions(c));
-    DevMatrix& A = c->A;
-    if (halves < 1 || halves > 2 || n < 1 || n * halves != A.n_local || nk < 0 || nk > kDriveMaxOps || !V0_dev ||
-        (nk > 0 && (!W_dev || !f || ldw < n)) || !A_dev || !partial)
-        return set_error(c, CAL_ERR_ARG, "diag_density_dev: bad arguments");
-    const bool real = halves == 1;  // the states are real vectors of n rows
-    if (A.shared) {  // both halves read one slot: it is written once, on H's rows
-        if (halves != 2)
-            return set_error(c, CAL_ERR_ARG, "diag_density_dev: a shared matrix takes both halves at once");
-        halves = 1;
-    }
-    DiagDensity a;
-    a.d.V0 = V0_dev;
-    a.d.W = W_dev;
-    a.d.ldw = ldw;
-    a.d.n = n;
-    a.d.nk = nk;
-    a.d.halves = halves;
-    for (int k = 0; k < nk; ++k) a.d.f[k] = f[k];
-    a.d.dpos = A.dpos;
-    a.d.val = A.val;
-    a.d.ds_diag = A.use_dsplit ? A.ds_diag : nullptr;
+    DiagDrive a = diag_drive_args(V0_dev, n, halves, nk, W_dev, ldw);
     a.A = A_dev;
     a.B = B_dev;
     a.ga = ga;
-    a.gb = B_dev ? gb : 0.0;
+    a.gb = gb;
     a.partial = partial;
-    a.real = real;
-    // the drive's bytes and the 2n (real: n) doubles of each state in; one partial per block out
-    const double bytes = (double)n * (8.0 * (1 + nk) + 4.0 * halves) + (double)n * halves * (A.use_dsplit ? 16.0 : 8.0) +
-                         (double)n * (real ? 8.0 : 16.0) * (B_dev ? 2 : 1) + 8.0 * diag_density_blocks(n);
-    const int t = timer_begin(c, 7, bytes);  // the drive's kind: the one launch that rewrites the diagonal
-    const hipError_t e = launch_diag_density(a, c->stream);
-    timer_end(c, t);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_diag_density");
-    return 0;
+    return diag_write_dev(c, "diag_density_dev", a, f, true);
 }
 
 int diag_gather_dev(cal_ctx* c, double* dst, int64_t cnt) {

@@ -608,7 +608,7 @@ int cal_prop_get_energetics(cal_ctx* ctx, int64_t first, int64_t count, double* 
  * several ranks; then an open propagator stays as it was. */
 int cal_prop_begin_real(cal_ctx* ctx, int64_t n, const double* psi, int s, int max_blocks, const char* basis,
                         const double* eigest, int neig);
-/* The real state's combine kernel (k_prop_combine_real) on host data, as
+/* The real state's combine kernel (k_prop_combine, REAL) on host data, as
  * cal_prop_combine_obs is for the stacked kernel: Q is n x m (ld n), a has m
  * entries (m <= 512),
  *   out[i] = sum_j Q[i,j] a_j     t = +0.0; j ascending: t = t + Q[i,j]*a_j

@@ -11,7 +11,7 @@ H[psi] = H0 + diag(sum_k f_k W_k) + g diag|psi|^2, N = ||psi_0||^2.
     stacked on blkdiag(H_j, H_j) from [Re; Im] or on H_j itself from a real
     state, the coefficients c = expm(-tau (T - T11 I)) e_1 by SciPy, the new
     state sqrt(N) Q c / ||c||_2 -- what the device build does.
-  * combine_real_ref: the real combine kernel's chain (k_prop_combine_real).
+  * combine_real_ref: the real combine kernel's chain (k_prop_combine, REAL).
   * energetics: mu, E_GP and the eigen-residual of a state from the true
     Rayleigh quotient, with the rounding bar of mu.
 """

@@ -1,6 +1,6 @@
 """The time-dependent potential H(t) = H0 + sum_k f_k(t) diag(W_k) on the device:
 cal_set_diagonal / cal_get_diagonal, cal_prop_set_drive, cal_prop_step_driven,
-cal_prop_refresh_shifts (kernels k_diag_find / k_diag_drive, prop.hip).
+cal_prop_refresh_shifts (kernels k_diag_find / k_diag_density without a state, prop.hip).
 
 Bars:
   * rewriting the diagonal is bit-exact: a context whose diagonal was rewritten

@@ -1,9 +1,9 @@
 """Imaginary-time propagation on the device: cal_prop_set_imaginary_time, the
-real-state path (cal_prop_begin_real, kernels k_prop_combine_real and
+real-state path (cal_prop_begin_real, kernels k_prop_combine<.., REAL> and
 k_diag_density<.., REAL>), the energetics rows and ground_state.
 
 Bars:
-  * k_prop_combine_real's out is the NumPy chain of tests/imagtime_ref.py
+  * k_prop_combine<.., REAL>'s out is the NumPy chain of tests/imagtime_ref.py
     combine_real_ref to the bit; norm2 and <W_k> within the derived rounding
     bar (N + 8) eps S of tests/prop_obs_ref.py.  The real density's diagonal is
     tests/nonlinear_ref.py density_chain with real states to the bit.
